@@ -16,6 +16,14 @@ Also: --config 3 (1024 x 8 MiB files, per-file blocks_hash on device),
 --config 4 (32 GiB shard per GPU of one 256 GiB file at 8 GPUs, RCCL gather
 of the 1.25 GiB table) and --config 5 (32 GiB, 64 KiB blocks).
 
+A plain run does only what the headline needs: it generates the input in
+HBM, warms up, times --steps steps, writes --dump-outputs DIR if asked (what
+the last timed step computed, as DIR/<name>.npy; the input is seeded, so two
+builds can be compared output for output) and prints the line.  --full adds,
+after the timed steps, the self-checks (digests and blocks_hash against the
+product's host SHA-1) and every side leg below from cpu_baseline on; in a
+plain line those fields are null.
+
 Rank 0 prints ONE JSON line (contract in the task statement), with:
   roofline      -- the SHA-1 kernel's algorithmic bytes / its average launch
                    time (HIP events on the launch stream) vs 8.0 TB/s HBM peak;
@@ -79,6 +87,43 @@ def valu_ceiling_gbs(bs):
     return SIMDS * MAX_CLOCK_HZ * 64 * bs / per_block / 1e9
 SEED = 0x5EED0000
 
+DUMP_MAX_BYTES = 64 * 1000 * 1000  # --dump-outputs: all .npy files of one run together
+DUMP_ROWS = 1 << 18  # rows kept of a table with more rows than this
+
+
+def dump_rows(n):
+    """The row numbers --dump-outputs keeps of an n-row table: every row, or a
+    fixed sample (seed SEED, ascending) that holds the first and the last row.
+    Depends on n alone, so two builds dump the same rows."""
+    import numpy as np
+    if n <= DUMP_ROWS:
+        return np.arange(n, dtype=np.int64)
+    rng = np.random.default_rng(SEED)
+    return np.unique(np.concatenate([[0, n - 1], rng.integers(0, n, DUMP_ROWS - 2)])).astype(np.int64)
+
+
+def dump_outputs(torch, out_dir, digests, file_hashes=None, weak=None):
+    """--dump-outputs: the arrays a caller of the timed path receives, as the
+    last timed step left them.  digests.npy: rows dump_rows() of the (blocks,
+    20) digest table, float32, one digest byte per element; digest_rows.npy:
+    those row numbers (float64); file_hashes.npy: config 3's per-file
+    blocks_hash, whole; weak.npy: --weak's Adler-32 sums of the same rows
+    (float64, exact)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    rows = dump_rows(digests.shape[0])
+    idx = torch.from_numpy(rows).to(digests.device)
+    arrays = {"digests": digests.index_select(0, idx).cpu().numpy().astype(np.float32),
+              "digest_rows": rows.astype(np.float64)}
+    if file_hashes is not None:
+        arrays["file_hashes"] = file_hashes.cpu().numpy().astype(np.float32)
+    if weak is not None:
+        arrays["weak"] = weak.index_select(0, idx).cpu().numpy().astype(np.uint32).astype(np.float64)
+    assert sum(v.nbytes for v in arrays.values()) <= DUMP_MAX_BYTES, "--dump-outputs: more than 64 MB"
+    for name, v in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), v)
+
+
 CONFIGS = {
     2: dict(workload="index one 8 GiB synthetic file, 4 KiB blocks (BASELINE configs[1])",
             bytes=8 * GiB, block=4096, files=1),
@@ -100,7 +145,17 @@ def parse():
     p.add_argument("--config", type=int, default=None, choices=sorted(CONFIGS),
                    help="default: 2 (configs[1]) at --gpus 1, 4 (configs[3], 32 GiB per GPU) at --gpus N > 1")
     p.add_argument("--shard-gib", type=float, default=None, help="override bytes per rank (GiB)")
-    p.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline time budget")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run every side leg and self-check (digest and blocks_hash "
+                        "self-checks, CPU baselines, config1, the end-to-end, content-defined-list and default-mode "
+                        "legs, e2e_file_multi on the library path; each still subject to its --no-* switch).  Off "
+                        "by default: a plain run sets up, warms up, times the steps and prints the line")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the last timed step computed as DIR/<name>.npy (float32 "
+                        "or float64, at most 64 MB in all): digests.npy, the digest table's rows (one byte per "
+                        "element; a fixed seeded sample of the rows when the table is larger) and "
+                        "digest_rows.npy, their row numbers; config 3 also file_hashes.npy, --weak also weak.npy")
+    p.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline time budget (--full)")
     p.add_argument("--ramp-s", type=float, default=0.5,
                    help="setup: keep the kernel busy this long before the warmup steps (the chip takes "
                         "~6 launches to ramp its clock from ~1.6 GHz; see DESIGN.md section 4)")
@@ -922,11 +977,12 @@ def _library_run(a, n, plan):
     # self-check: the last step's table (device 0's) against every shard's
     # first and last block (product host SHA-1) and, for the other devices,
     # against their scratch table of that step
+    # (--full only, as the host blocks_hash stage and the e2e_file_multi leg)
     b_last = (a.steps - 1) % 3
     assert last[0][0] == roots[-1]
     tab = tables[last[0][0]][last[0][1]][:nb_total]
     for r, sh in enumerate(plan["shards"]):
-        if not sh["rows"]:
+        if not a.full or not sh["rows"]:
             continue
         rows = tab[sh["first_row"]: sh["first_row"] + sh["rows"]].cpu().numpy()
         first = data[r][:bs].cpu().numpy()
@@ -934,14 +990,18 @@ def _library_run(a, n, plan):
         assert bytes(rows[0]) == host.sha1(first) and bytes(rows[-1]) == host.sha1(lastb), f"device {r} digests"
         if r != roots[-1]:
             assert np.array_equal(rows, digs[r][b_last][: sh["rows"]].cpu().numpy()), f"device {r} gather"
-    full = tab.cpu().numpy()
-    tb = time.perf_counter()
-    host.blocks_hash(full)
-    bh_ms = (time.perf_counter() - tb) * 1e3
-    del full
+    if a.dump_outputs:  # the last timed step's table, as its root received it
+        dump_outputs(torch, a.dump_outputs, tab)
+    bh_ms = None
+    if a.full:
+        full = tab.cpu().numpy()
+        tb = time.perf_counter()
+        host.blocks_hash(full)
+        bh_ms = (time.perf_counter() - tb) * 1e3
+        del full
 
     e2e = None
-    if a.e2e_multi_gib > 0 and not a.no_e2e:
+    if a.full and a.e2e_multi_gib > 0 and not a.no_e2e:
         try:  # a side leg: its failure (a full /tmp) must not cost the measured line
             e2e = e2e_file_multi(data, n, bs, a.e2e_multi_gib)
         except Exception as e:  # noqa: BLE001
@@ -998,8 +1058,9 @@ def _library_run(a, n, plan):
         "code_object_sha256": code_object_sha256(),
         "kernel_code_sha256": kcode,
         "events": "step",
+        "full": a.full,  # false: the self-checks, blocks_hash_host_ms and e2e_file_multi are not run (null)
         "hbm_frac_of_peak": round(per / (t / a.steps) / 1e9 / HBM_PEAK_GBS, 4),
-        "blocks_hash_host_ms": round(bh_ms, 2),
+        "blocks_hash_host_ms": round(bh_ms, 2) if bh_ms is not None else None,
         "e2e_file_multi": e2e,
     }
     print(json.dumps(line), flush=True)
@@ -1321,18 +1382,20 @@ def torch_main(a, fallback_note=None):
     dig = digs[(a.steps - 1) % nbuf]
     gathered = last_table[0]() if last_table[0] is not None else None
 
-    if int(status.item()) != 0:
-        raise SystemExit(f"staged batch status word changed to {int(status.item())} (it is never written)")
-    # Self-check (product host SHA-1): first and last block of this shard.
-    d = dig.cpu().numpy()
-    first = data[:bs].cpu().numpy()
-    lastb = data[(nblk - 1) * bs:].cpu().numpy()
-    assert bytes(d[0]) == host.sha1(first) and bytes(d[-1]) == host.sha1(lastb), "digest self-check failed"
-    if files is not None:  # the last batch's per-file blocks_hash (device) vs the host SHA-1 of its rows
-        per_file = d.reshape(len(files), -1, 20)
-        fh = (last_hashes[0] if bstream is not None else fhash).cpu().numpy()
-        for f in (0, len(files) - 1):
-            assert bytes(fh[f]) == host.blocks_hash(per_file[f]), "blocks_hash self-check failed"
+    d = None
+    if a.full:
+        if int(status.item()) != 0:
+            raise SystemExit(f"staged batch status word changed to {int(status.item())} (it is never written)")
+        # Self-check (product host SHA-1): first and last block of this shard.
+        d = dig.cpu().numpy()
+        first = data[:bs].cpu().numpy()
+        lastb = data[(nblk - 1) * bs:].cpu().numpy()
+        assert bytes(d[0]) == host.sha1(first) and bytes(d[-1]) == host.sha1(lastb), "digest self-check failed"
+        if files is not None:  # the last batch's per-file blocks_hash (device) vs the host SHA-1 of its rows
+            per_file = d.reshape(len(files), -1, 20)
+            fh = (last_hashes[0] if bstream is not None else fhash).cpu().numpy()
+            for f in (0, len(files) - 1):
+                assert bytes(fh[f]) == host.blocks_hash(per_file[f]), "blocks_hash self-check failed"
 
     if rank != 0:
         if distributed:
@@ -1341,13 +1404,18 @@ def torch_main(a, fallback_note=None):
 
     if gather and gathered is None:
         raise SystemExit("rank 0 received no table from the last step's gather")
-    if gathered is not None:  # rank 0 owns the whole file's table, rank order
+    if a.full and gathered is not None:  # rank 0 owns the whole file's table, rank order
         assert gathered.shape[0] == total // bs and torch.equal(gathered[:nblk].to(dig.device), dig)
+
+    if a.dump_outputs:  # the last timed step's table (rank 0's gathered one at N > 1) and what came with it
+        dump_outputs(torch, a.dump_outputs, gathered if gathered is not None else dig,
+                     file_hashes=None if files is None else (last_hashes[0] if bstream is not None else fhash),
+                     weak=weaks[(a.steps - 1) % nbuf] if weaks is not None and gathered is None else None)
 
     # Host stage of the single-file path: blocks_hash over all digests
     # (sequential SHA-1, reported separately, not in `value`).
     bh_ms = None
-    if files is None:
+    if a.full and files is None:
         full = gathered.cpu().numpy() if gathered is not None else d
         tb = time.perf_counter()
         host.blocks_hash(full)
@@ -1377,18 +1445,19 @@ def torch_main(a, fallback_note=None):
             traffic = ent["hbm_bytes_per_launch"]
     except (OSError, ValueError):
         pass
+    # Everything below the line's own figures runs under --full only.
     cdc = None
-    if not a.no_cdc_list and world == 1 and files is None and weaks is None and a.config == 2:
+    if a.full and not a.no_cdc_list and world == 1 and files is None and weaks is None and a.config == 2:
         cdc = content_defined_list(torch, data, stream)
     e2e = None
-    if not a.no_e2e and world == 1 and files is None and weaks is None:
+    if a.full and not a.no_e2e and world == 1 and files is None and weaks is None:
         e2e = e2e_host_buffer(torch, data, d, bs)
     dmode = None
-    if not a.no_default_mode and world == 1 and files is None and weaks is None and a.config == 2:
+    if a.full and not a.no_default_mode and world == 1 and files is None and weaks is None and a.config == 2:
         dmode = default_mode_files(data, max(1, min(16, len(os.sched_getaffinity(0)))))
     cpu = cpu_all = cpu_ni = cpu_ni_all = None
-    config1 = config1_probe() if world == 1 else None
-    if not a.no_cpu_baseline and world == 1:
+    config1 = config1_probe() if a.full and world == 1 else None
+    if a.full and not a.no_cpu_baseline and world == 1:
         threads = max(1, min(16, len(os.sched_getaffinity(0))))
         cpu = cpu_baseline(shard, bs, a.cpu_seconds)
         cpu_all = cpu_baseline_all_cores(shard, bs, a.cpu_seconds / 4)
@@ -1442,6 +1511,7 @@ def torch_main(a, fallback_note=None):
         "code_object_sha256": kernels,
         "kernel_code_sha256": kcode,
         "events": a.events,
+        "full": a.full,  # false: the fields of the side legs and self-checks are null (not run)
         "multi": multi,
         "hbm_frac_of_peak": round(total_bytes / world / (t / a.steps) / 1e9 / HBM_PEAK_GBS, 4),
         "blocks_hash_host_ms": round(bh_ms, 2) if bh_ms is not None else None,

@@ -22,14 +22,14 @@ if [ -z "$SKIP_BASE" ]; then  # SKIP_BASE=1: only the optional steps below
 run pytest_gpu 900 python -u -m pytest tests -m gpu -q -x -p no:cacheprovider --timeout 150 --timeout-method thread
 rc=$?; if [ $rc -ge 2 ]; then exit $rc; fi
 run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" || exit $?
-run bench 600 python bench.py --steps "$STEPS" --warmup 2 --cpu-seconds 8 || exit $?
+run bench 600 python bench.py --full --steps "$STEPS" --warmup 2 --cpu-seconds 8 || exit $?
 fi
 if [ -n "$EXTRA" ]; then
-  run bench_c3 600 python bench.py --config 3 --steps "$STEPS" --warmup 2 --no-cpu-baseline || exit $?
-  run bench_c5 600 python bench.py --config 5 --steps 5 --warmup 1 --no-cpu-baseline || exit $?
+  run bench_c3 600 python bench.py --full --config 3 --steps "$STEPS" --warmup 2 --no-cpu-baseline || exit $?
+  run bench_c5 600 python bench.py --full --config 5 --steps 5 --warmup 1 --no-cpu-baseline || exit $?
   # N>1 code path rehearsal on one GPU: bench.py starts its 2 ranks itself,
   # both share cuda:0, gloo gather
-  run bench_rehearsal2 600 python bench.py --gpus 2 --steps 5 --warmup 1 --shard-gib 1 --dist-backend gloo --no-cpu-baseline || exit $?
+  run bench_rehearsal2 600 python bench.py --full --gpus 2 --steps 5 --warmup 1 --shard-gib 1 --dist-backend gloo --no-cpu-baseline || exit $?
 fi
 if [ -n "$ASAN" ]; then
   # host-side ASan + UBSan of the C-ABI's host pipelines (make -C examples asan first)

@@ -161,6 +161,40 @@ def test_multi_path_resolution():
     assert ns(gpus=8, config=2).config == 2
 
 
+def test_dump_rows_fixed_sample_within_the_size_limit():
+    """--dump-outputs keeps every row of a small table and a fixed, seeded,
+    ascending sample (first and last row included) of a larger one, so two
+    runs dump the same rows; a sampled dump (float32 digests, float64 row
+    numbers and weak sums) stays under the 64 MB limit."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+
+    import bench
+    assert bench.dump_rows(0).size == 0
+    assert bench.dump_rows(bench.DUMP_ROWS).tolist() == list(range(bench.DUMP_ROWS))
+    for n in (bench.DUMP_ROWS + 1, (8 << 30) // 4096, (256 << 30) // 4096):
+        rows = bench.dump_rows(n)
+        assert rows.dtype == np.int64 and np.array_equal(rows, bench.dump_rows(n))
+        assert rows[0] == 0 and rows[-1] == n - 1 and np.all(np.diff(rows) > 0)
+        assert bench.DUMP_ROWS // 2 < rows.size <= bench.DUMP_ROWS
+    assert bench.DUMP_ROWS * (20 * 4 + 8 + 8) + 1024 * 20 * 4 <= bench.DUMP_MAX_BYTES
+
+
+def test_plain_run_is_the_default():
+    # the side legs and self-checks run under --full only; --dump-outputs is off unless given
+    sys.path.insert(0, ROOT)
+    import bench
+    argv, sys.argv = sys.argv, ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"]
+    try:
+        a = bench.parse()
+        sys.argv = ["bench.py", "--full", "--dump-outputs", "d"]
+        b = bench.parse()
+    finally:
+        sys.argv = argv
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 2)
+    assert (b.full, b.dump_outputs) == (True, "d")
+
+
 def test_torchrun_library_failure_falls_back_on_every_rank():
     """The driver's torchrun with the library path: rank 0 drives every device
     in one process and the other ranks wait.  If rank 0's path fails for any

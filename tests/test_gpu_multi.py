@@ -116,7 +116,7 @@ def test_bench_library_path_one_device(gpu, self_gather):
     env["SF_TEST_MULTI_SELF_GATHER"] = self_gather
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--multi-path", "library",
                         "--shard-gib", "0.25", "--steps", "6", "--warmup", "2", "--ramp-s", "0.05",
-                        "--e2e-multi-gib", "0.125"], capture_output=True, text=True, timeout=110, env=env)
+                        "--e2e-multi-gib", "0.125", "--full"], capture_output=True, text=True, timeout=110, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert line["n_gpus"] == 1 and line["value"] > 0 and line["config"]["total_bytes"] == 1 << 28

@@ -80,7 +80,7 @@ def test_bench_self_launches_two_ranks(gpu):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dist-backend", "gloo",
                         "--shard-gib", "0.0625", "--steps", "3", "--warmup", "1", "--ramp-s", "0",
-                        "--no-cpu-baseline"], capture_output=True, text=True, timeout=110, env=env)
+                        "--no-cpu-baseline", "--full"], capture_output=True, text=True, timeout=110, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert line["n_gpus"] == 2 and line["config"]["total_bytes"] == 2 * (64 << 20)
