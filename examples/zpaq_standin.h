@@ -16,7 +16,10 @@
  * per-byte work as the crate's loop, so it stands in for the crate's COST in
  * the configs[0] baseline and in the default mode's end-to-end record; its
  * boundaries are not the reference's (first cut 5,908 on the KAT input
- * instead of 11,579).
+ * instead of 11,579).  The crate's real recurrence, which does reproduce the
+ * known-answer test, now lives in the library (sf_zpaq_cut_buffer,
+ * sf_zpaq_chunker_ops, include/syncfast_amd.h; examples/zpaq_cut.c); this
+ * header stays as the timing stand-in bench.py and oracle/ are built on.
  *
  * Header-only C; used by examples/sf_index.c (-Z) and oracle/sf_baseline.cpp. */
 #ifndef ZPAQ_STANDIN_H

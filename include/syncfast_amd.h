@@ -466,6 +466,78 @@ void sf_free_cuts(void *p);
 int sf_index_fd_cut(int fd, const sf_file_stamp *expect, const sf_chunker_ops *ops, uint32_t threads,
                     sf_block_sig **rows, uint64_t *n_out, uint8_t blocks_hash[SF_HASH_DIGEST_LEN]);
 
+/* ------------------- the reference's chunker itself: host and device ---- */
+
+/* cdchunking's ZPAQ chunker as index_file configures it (src/index.rs:622-625:
+ * bits = 13, max_size = 32768), in the library.  Per input byte b, with h
+ * (32 bits), c1 (the previous byte) and o1[256] (the byte that last followed
+ * each byte):  h = h * (b == o1[c1] ? M : 2 * M) + b + 1, M = 123456791;
+ * o1[c1] = b; c1 = b;  the chunk ends AFTER b when h < 2^(32 - bits) or its
+ * length reaches max_size.  A chunk starts with h = M, c1 = 0, o1 all 0, and
+ * the state is that again after every cut.  This reproduces the reference's
+ * known-answer test (src/index.rs:761-792) exactly; the restart at a cut is
+ * the one point that test does not pin.
+ *
+ * sf_zpaq_cut_buffer: the blocks of data[0, len), sequentially, on the calling
+ * thread -- the library's definition of the boundaries; every other route
+ * (sf_cut_fd over the ops below, the device cutter) returns exactly this
+ * list.  offsets / sizes: cap entries; *n_blocks = the count (the need, with
+ * SF_ENOSPC and the first cap rows written, when cap is too small or the
+ * arrays are NULL).  The last block ends at len; len == 0 gives 0 blocks.
+ * SF_EINVAL unless 1 <= bits <= 31 and max_size >= 1.  Host only. */
+int sf_zpaq_cut_buffer(const uint8_t *data, uint64_t len, uint32_t bits, uint32_t max_size,
+                       uint64_t *offsets, uint32_t *sizes, uint64_t cap, uint64_t *n_blocks);
+
+/* The same chunker as an sf_chunker_ops: with it sf_cut_fd, sf_index_fd_cut
+ * and (per file) sf_index_fds_blocks produce the reference's boundaries on N
+ * host threads, and a Rust caller needs no chunker of its own.  The
+ * parameters are carried in out->ctx itself (packed into the pointer's value:
+ * nothing is allocated, there is nothing to release, and the struct may be
+ * copied freely); each create() allocates one chunker state, freed by
+ * destroy().  SF_EINVAL as above. */
+int sf_zpaq_chunker_ops(uint32_t bits, uint32_t max_size, sf_chunker_ops *out);
+
+/* The same boundaries for bytes already in HBM, cut on the device: blocks of
+ * d_data[0, len) as (d_offsets uint64, d_sizes uint32) in file order --
+ * exactly the list sf_index_device_blocks takes -- with the last block ending
+ * at len.  The buffer is cut speculatively in segments (one lane each) whose
+ * lists are then joined in rounds, each a kernel (sf_cdc.hip); the result is
+ * sf_zpaq_cut_buffer's for any input.  BLOCKING: `stream` is synchronised
+ * once per join round and once for the count.  Random or text-like data
+ * joins in 1-3 rounds; constant or periodic data needs one round per segment
+ * (segments are lcm(max_size, 32) bytes) and is cut at the speed of a single
+ * lane -- still exact.  d_data needs no alignment.  *n_blocks = the count;
+ * SF_ENOSPC (nothing written) when cap_blocks is smaller or an output is NULL.
+ * len == 0 gives 0 blocks.  SF_EINVAL unless 1 <= bits <= 31 and
+ * 16 <= max_size <= 1048576 (the device range).  Scratch: len / 4 bytes plus
+ * 56 bytes per segment, from the library's stream-ordered pool. */
+int sf_cut_device_zpaq(const void *d_data, uint64_t len, uint32_t bits, uint32_t max_size,
+                       uint64_t *d_offsets, uint32_t *d_sizes, uint64_t cap_blocks,
+                       uint64_t *n_blocks, void *stream);
+
+/* index_file's default mode (src/index.rs:621-656) for bytes already in HBM:
+ * sf_cut_device_zpaq, then the explicit-list kernel over that list
+ * (sf_index_device_blocks) into d_digests (cap_blocks x 20 B), then, if
+ * blocks_hash (a HOST pointer, may be NULL) is given, the digests are copied
+ * back and chained on the host (compute_blocks_hash, src/index.rs:661-682).
+ * Blocking as sf_cut_device_zpaq; errors as there. */
+int sf_index_device_zpaq(const void *d_data, uint64_t len, uint32_t bits, uint32_t max_size,
+                         uint64_t *d_offsets, uint32_t *d_sizes, void *d_digests, uint64_t cap_blocks,
+                         uint64_t *n_blocks, uint8_t *blocks_hash, void *stream);
+
+/* index_file in the default mode for one regular file open on fd, with no
+ * host chunker at all: the file is read once (pread, the library's reader
+ * threads) into pinned memory and copied to HBM by windows of up to 512 MiB;
+ * each window is cut (sf_cut_device_zpaq) and hashed on the device.  A
+ * non-final window's last block was closed by the window's end, so it is
+ * dropped and the next window starts at its offset -- a true cut, so the rows
+ * are exactly sf_index_fd_cut's with sf_zpaq_chunker_ops.  *rows (n_out
+ * entries, release with sf_free_rows) and blocks_hash as there; expect,
+ * SF_EAGAIN and the other errors as sf_cut_fd; bits / max_size as
+ * sf_cut_device_zpaq.  Blocking. */
+int sf_index_fd_zpaq(int fd, const sf_file_stamp *expect, uint32_t bits, uint32_t max_size,
+                     sf_block_sig **rows, uint64_t *n_out, uint8_t blocks_hash[SF_HASH_DIGEST_LEN]);
+
 /* ------------------------------------------- one process, N devices ---- */
 
 /* Contiguous, block-aligned shard `shard` of n_shards of a file_len-byte file:

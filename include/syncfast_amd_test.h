@@ -73,6 +73,13 @@ int sf_test_multi_plan(uint64_t file_len, uint32_t block_size, uint32_t n_device
  * gives out[4] == out[3] < out[2] == out[5]. */
 int sf_test_xcd_litmus(int mode, uint32_t out[8]);
 
+/* What the device ZPAQ cutter (sf_cut_device_zpaq and the calls built on it)
+ * did in its most recent cut in this process: out[0] the segment length in
+ * bytes (lcm(max_size, 32)), out[1] the number of segments, out[2] the join
+ * rounds in which a segment cut again, out[3] the bytes cut again in all of
+ * them.  Host only; not synchronised with cuts in flight. */
+int sf_test_zpaq_device_stats(uint64_t out[4]);
+
 #ifdef __cplusplus
 }
 #endif

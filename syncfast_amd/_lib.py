@@ -38,12 +38,13 @@ EXPORTED = (
     "sf_index_device_multi", "sf_index_device_multi_ex",
     "sf_blocks_hash", "sf_blocks_hash_sigs", "sf_sha1_host",
     "sf_block_set_build", "sf_block_set_lookup", "sf_block_set_free",
+    "sf_zpaq_cut_buffer", "sf_zpaq_chunker_ops", "sf_cut_device_zpaq", "sf_index_device_zpaq", "sf_index_fd_zpaq",
 )
 # Test hooks (include/syncfast_amd_test.h): knobs latched at load, route counters,
 # the explicit-list processing order.
 EXPORTED_TEST = ("sf_test_set_knob", "sf_test_get_knob", "sf_test_get_stat", "sf_test_table_order",
                  "sf_test_table_order_bits",
-                 "sf_test_set_read_hook", "sf_test_xcd_litmus", "sf_test_multi_plan")
+                 "sf_test_set_read_hook", "sf_test_xcd_litmus", "sf_test_multi_plan", "sf_test_zpaq_device_stats")
 
 
 class SfError(OSError):
@@ -143,6 +144,12 @@ def _declare(L: ctypes.CDLL) -> None:
     L.sf_block_set_build.argtypes = [vp, vp, u64, ctypes.POINTER(vp), vp]
     L.sf_block_set_lookup.argtypes = [vp, vp, u64, vp, vp]
     L.sf_block_set_free.argtypes = [vp, vp]
+    L.sf_zpaq_cut_buffer.argtypes = [vp, u64, u32, u32, vp, vp, u64, pu64]
+    L.sf_zpaq_chunker_ops.argtypes = [u32, u32, vp]
+    L.sf_cut_device_zpaq.argtypes = [vp, u64, u32, u32, vp, vp, u64, pu64, vp]
+    L.sf_index_device_zpaq.argtypes = [vp, u64, u32, u32, vp, vp, vp, u64, pu64, vp, vp]
+    L.sf_index_fd_zpaq.argtypes = [i32, vp, u32, u32, ctypes.POINTER(ctypes.POINTER(BlockSig)), pu64, vp]
+    L.sf_test_zpaq_device_stats.argtypes = [vp]
     pi64 = ctypes.POINTER(ctypes.c_int64)
     L.sf_test_set_knob.argtypes = [ctypes.c_char_p, ctypes.c_int64, pi64]
     L.sf_test_get_knob.argtypes = [ctypes.c_char_p, pi64]

@@ -1,0 +1,620 @@
+// sf_cdc.hip -- the reference's content-defined (ZPAQ) block boundaries cut on
+// the device (include/syncfast_amd.h: sf_cut_device_zpaq, sf_index_device_zpaq,
+// sf_index_fd_zpaq).  Its own translation unit: the SHA-1 kernels' code objects
+// stay as they are.
+//
+// The per-byte chain (sf_zpaq_step.hpp) is serial from each chunk's first
+// byte, and the chunker restarts at every cut, so the boundaries are a
+// function of where a chunk starts.  Parallelism comes from segments, as in
+// sf_cut_fd's host join (sf_cut.cpp), with kernel boundaries as the only
+// dependencies -- no kernel waits for another wave:
+//
+//   round 0   the buffer is split into segments of L bytes, L = the least
+//             common multiple of max_size and 32 (a function of max_size
+//             only; every full segment holds at least one cut, and a segment
+//             owns whole words of the cut bitmaps).  One lane per segment
+//             cuts it from its first byte with a fresh state and records, as
+//             bits, the cuts that end in (s0, s0 + L] -- its speculative list.
+//   join      segment s takes as its incoming cut the last cut of segment
+//             s - 1's current list (of the previous round: the lists' last
+//             cuts are double-buffered).  If that differs from the one it used
+//             last, it cuts again from there with a fresh state until a cut
+//             coincides with one of its round-0 cuts, adopts the rest of the
+//             round-0 list from there, or keeps its own cuts if none
+//             coincides before the segment ends.  The host reads one
+//             changed-count per round and repeats until it is 0.  By
+//             induction from segment 0 (whose round-0 list is true) the fixed
+//             point is the sequential list, reached in at most nseg rounds.
+//   compact   per-segment counts, a prefix sum, and one lane per segment
+//             writes its (offset, size) rows in file order; the last block
+//             ends at len.
+//
+// Every loop is bounded by a segment's length (+ max_size for a join's run-in),
+// by len or by nseg.
+//
+// Constant or periodic data is serial in rounds: speculative and true cuts
+// never coincide on it, so the join advances ONE segment per round
+// (nseg - 1 rounds, one lane working in each).  The result stays exact; the
+// time is that of a single lane walking the buffer plus a kernel boundary and
+// a host read per segment (DESIGN.md 3.7 has the measured figure).
+//
+// Kernel shape: a wave per workgroup, a lane per segment.  Per lane h, c1, the
+// run length and the 256-byte order-1 table in LDS (16 KiB per wave), laid out
+// so that lane l only ever touches bank l mod 32: entry e of lane l is byte
+// (e >> 2) * 256 + l * 4 + (e & 3).  Lanes read their own segments (stride L)
+// 16 bytes at a time where the address allows, 64 bytes ahead of the bytes
+// being fed.  The table's lookups and updates depend on the data only, not on
+// h, so 16 bytes are fed with no branch (LaneChunker::feed16): the LDS
+// traffic is one in-order stream beside the multiply chain, and a cut inside
+// the 16 bytes is found afterwards (the table is wiped at a cut anyway).
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <string.h>
+#include <sys/stat.h>
+#include <unistd.h>
+#include <errno.h>
+
+#include <rocprim/device/device_scan.hpp>
+
+#include <memory>
+
+#include "host_sha1.h"
+#include "sf_internal.hpp"
+#include "sf_zpaq_step.hpp"
+#include "../../include/syncfast_amd_test.h"
+
+namespace {
+
+constexpr uint32_t kLanes = 64;           // one wave per workgroup
+constexpr uint32_t kMinMaxSize = 16;      // device range of max_size
+constexpr uint32_t kMaxMaxSize = 1u << 20;
+
+struct Counters {
+  unsigned long long recut;  // bytes cut again in joins (all rounds)
+  uint32_t changed;          // segments that cut again this round
+  uint32_t pad;
+};
+
+// One lane's chunker: the order-1 table lives in LDS at tab[...] (see the
+// file comment for the layout; tab already points at this lane's column).
+struct LaneChunker {
+  uint8_t* tab;
+  uint32_t lim, max_size, h, c1, run;
+  __device__ __forceinline__ void fresh() {
+    h = sfz::kFreshH;
+    c1 = 0;
+    run = 0;
+    uint32_t* t = reinterpret_cast<uint32_t*>(tab);
+#pragma unroll 8
+    for (uint32_t k = 0; k < 64; k++) t[k * kLanes] = 0;
+  }
+  __device__ __forceinline__ uint8_t* entry(uint32_t c) const { return tab + ((c >> 2) << 8) + (c & 3); }
+  // feeds one byte; true: the chunk ends after it (the state is fresh again)
+  __device__ __forceinline__ bool feed(uint32_t b) {
+    uint8_t* e = entry(c1);
+    h = sfz::step(h, b, *e);
+    *e = (uint8_t)b;
+    c1 = b;
+    run++;
+    if (!sfz::cuts(h, lim, run, max_size)) return false;
+    fresh();
+    return true;
+  }
+  // Feeds 16 bytes with no branch per byte: the table's reads and writes
+  // depend on the data only, not on h, so they form one in-order LDS stream
+  // whose latency overlaps the multiply chain.  Returns the index of the
+  // first byte that ends a chunk (the state is then fresh: the table writes
+  // made for the bytes after it are wiped with the rest), or 16.
+  __device__ __forceinline__ uint32_t feed16(const uint4& v) {
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+    uint32_t pr[16], c = c1;
+#pragma unroll
+    for (uint32_t k = 0; k < 16; k++) {
+      const uint32_t b = (w[k >> 2] >> (8 * (k & 3))) & 0xFFu;
+      uint8_t* e = entry(c);
+      pr[k] = *e;
+      *e = (uint8_t)b;
+      c = b;
+    }
+    uint32_t hh = h, first = 16;
+#pragma unroll
+    for (uint32_t k = 0; k < 16; k++) {
+      hh = sfz::step(hh, (w[k >> 2] >> (8 * (k & 3))) & 0xFFu, pr[k]);
+      const bool ct = sfz::cuts(hh, lim, run + k + 1, max_size);
+      first = ct && first == 16 ? k : first;
+    }
+    if (first == 16) {
+      h = hh;
+      c1 = c;
+      run += 16;
+    } else {
+      fresh();
+    }
+    return first;
+  }
+  // The 64 bytes fetched ahead: rk = the 16 bytes at rpos + 16 k, loaded
+  // while they lie below hi.
+  uint4 r0, r1, r2, r3;
+  uint64_t rpos;
+  // Feeds ONE unit of bytes [p, hi) (hi <= the buffer's length; the same hi
+  // in every call of a run): 16 bytes where the address is 16-byte aligned
+  // and they are all in range, else 1.  Returns the position after the unit
+  // and cut = false, or the position after the byte that ends a chunk and
+  // cut = true.  One unit per call keeps the caller's loop flat: lanes on the
+  // two paths, or just past a cut, cost each other one iteration, not a run.
+  __device__ __forceinline__ uint64_t advance(const uint8_t* __restrict__ data, uint64_t p, uint64_t hi, bool& cut) {
+    if (((reinterpret_cast<uintptr_t>(data + p) & 15) == 0) && hi - p >= 16) {
+      const uint4* q = reinterpret_cast<const uint4*>(data + p);
+      if (rpos != p) {
+        r0 = q[0];
+        if (hi - p >= 32) r1 = q[1];
+        if (hi - p >= 48) r2 = q[2];
+        if (hi - p >= 64) r3 = q[3];
+      }
+      const uint4 v = r0;
+      r0 = r1;
+      r1 = r2;
+      r2 = r3;
+      if (hi - p >= 80) r3 = q[4];
+      rpos = p + 16;
+      const uint32_t j = feed16(v);
+      cut = j < 16;
+      return cut ? p + j + 1 : p + 16;
+    }
+    cut = feed((uint32_t)data[p]);
+    return p + 1;
+  }
+};
+
+// Bit i of a cut bitmap = a chunk ends after byte i.  Segment s owns words
+// [s * L / 32, ceil(min(len, (s + 1) * L) / 32)).  A segment's cuts arrive in
+// increasing order; the words between them are zero.
+struct CutWriter {
+  uint32_t* a;
+  uint32_t* b;  // a second bitmap that gets the same words, or NULL
+  uint64_t w;   // the word being gathered
+  uint32_t acc;
+  __device__ __forceinline__ void store(uint64_t k, uint32_t v) {
+    a[k] = v;
+    if (b) b[k] = v;
+  }
+  __device__ __forceinline__ void advance(uint64_t wi) {  // w < wi: words [w, wi) are complete
+    store(w, acc);
+    for (uint64_t k = w + 1; k < wi; k++) store(k, 0u);
+    w = wi;
+    acc = 0;
+  }
+  __device__ __forceinline__ void put(uint64_t i) {  // a chunk ends after byte i
+    if ((i >> 5) != w) advance(i >> 5);
+    acc |= 1u << (i & 31);
+  }
+  __device__ __forceinline__ void finish(uint64_t wend) { advance(wend + 1); }  // through word wend
+};
+
+__global__ void __launch_bounds__(kLanes) zpaq_round0_kernel(const uint8_t* __restrict__ data, uint64_t len, uint64_t L,
+                                                             uint64_t nseg, uint32_t lim, uint32_t max_size,
+                                                             uint32_t* __restrict__ spec, uint32_t* __restrict__ cur,
+                                                             uint64_t* __restrict__ last, uint64_t* __restrict__ lastspec,
+                                                             uint64_t* __restrict__ used) {
+  __shared__ uint8_t lds[kLanes * 256];
+  const uint64_t s = (uint64_t)blockIdx.x * kLanes + threadIdx.x;
+  if (s >= nseg) return;
+  const uint64_t s0 = s * L, s1 = s0 + L < len ? s0 + L : len;
+  LaneChunker z;
+  z.tab = lds + threadIdx.x * 4;
+  z.lim = lim;
+  z.max_size = max_size;
+  z.fresh();
+  z.rpos = ~0ull;
+  z.r0 = z.r1 = z.r2 = z.r3 = uint4{0, 0, 0, 0};
+  CutWriter wr{spec, cur, s0 >> 5, 0u};
+  uint64_t lastcut = s0;
+  for (uint64_t p = s0; p < s1;) {
+    bool cut;
+    p = z.advance(data, p, s1, cut);
+    if (cut) {
+      wr.put(p - 1);
+      lastcut = p;
+    }
+  }
+  wr.finish((s1 - 1) >> 5);
+  if (s1 == len) cur[(len - 1) >> 5] |= 1u << ((len - 1) & 31);  // the last block ends at len
+  last[s] = lastcut;
+  lastspec[s] = lastcut;
+  used[s] = s0;
+}
+
+__global__ void __launch_bounds__(kLanes) zpaq_join_kernel(const uint8_t* __restrict__ data, uint64_t len, uint64_t L,
+                                                           uint64_t nseg, uint32_t lim, uint32_t max_size,
+                                                           const uint32_t* __restrict__ spec, uint32_t* __restrict__ cur,
+                                                           const uint64_t* __restrict__ last_in,
+                                                           uint64_t* __restrict__ last_out,
+                                                           const uint64_t* __restrict__ lastspec,
+                                                           uint64_t* __restrict__ used, Counters* __restrict__ ctr) {
+  __shared__ uint8_t lds[kLanes * 256];
+  const uint64_t s = (uint64_t)blockIdx.x * kLanes + threadIdx.x;
+  if (s >= nseg) return;
+  if (s == 0) {  // segment 0 starts at byte 0: its round-0 list is the true one
+    last_out[0] = last_in[0];
+    return;
+  }
+  const uint64_t inc = last_in[s - 1];  // in (s0 - max_size, s0]
+  if (inc == used[s]) {
+    last_out[s] = last_in[s];
+    return;
+  }
+  used[s] = inc;
+  atomicAdd(&ctr->changed, 1u);
+  const uint64_t s0 = s * L, s1 = s0 + L < len ? s0 + L : len, wend = (s1 - 1) >> 5;
+  LaneChunker z;
+  z.tab = lds + threadIdx.x * 4;
+  z.lim = lim;
+  z.max_size = max_size;
+  z.fresh();
+  z.rpos = ~0ull;
+  z.r0 = z.r1 = z.r2 = z.r3 = uint4{0, 0, 0, 0};
+  CutWriter wr{cur, nullptr, s0 >> 5, 0u};
+  uint64_t lastcut = inc, p = inc;
+  bool synced = false;
+  while (p < s1) {
+    bool cut;
+    p = z.advance(data, p, s1, cut);
+    if (!cut || p <= s0) continue;  // no cut, or the run-in: the previous segment's bytes
+    const uint64_t i = p - 1;
+    wr.put(i);
+    lastcut = p;
+    if (spec[i >> 5] & (1u << (i & 31))) {  // one of the round-0 cuts: the rest of that list follows
+      synced = true;
+      break;
+    }
+  }
+  if (synced) {
+    const uint64_t i = p - 1, w = i >> 5;
+    const uint32_t above = (i & 31) == 31 ? 0u : ~0u << ((i & 31) + 1);
+    cur[w] = wr.acc | (spec[w] & above);
+    for (uint64_t k = w + 1; k <= wend; k++) cur[k] = spec[k];
+    lastcut = lastspec[s];
+  } else {
+    wr.finish(wend);
+  }
+  if (s1 == len) cur[(len - 1) >> 5] |= 1u << ((len - 1) & 31);  // the last block ends at len
+  atomicAdd(&ctr->recut, (unsigned long long)(p - inc));
+  last_out[s] = lastcut;
+}
+
+__global__ void __launch_bounds__(256) zpaq_count_kernel(const uint32_t* __restrict__ cur, uint64_t len, uint64_t L,
+                                                         uint64_t nseg, uint64_t* __restrict__ counts) {
+  const uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= nseg) return;
+  const uint64_t s0 = s * L, s1 = s0 + L < len ? s0 + L : len;
+  uint64_t n = 0;
+  for (uint64_t w = s0 >> 5; w <= (s1 - 1) >> 5; w++) n += (uint64_t)__popc(cur[w]);
+  counts[s] = n;
+}
+
+// ends[s] = number of blocks ending in segments 0..s (inclusive scan of the
+// counts); segment s writes rows [ends[s - 1], ends[s]).  Its first block
+// starts at the last cut of segment s - 1 (every full segment has one).
+__global__ void __launch_bounds__(256) zpaq_emit_kernel(const uint32_t* __restrict__ cur, uint64_t len, uint64_t L,
+                                                        uint64_t nseg, const uint64_t* __restrict__ ends,
+                                                        const uint64_t* __restrict__ last, uint64_t* __restrict__ offsets,
+                                                        uint32_t* __restrict__ sizes) {
+  const uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= nseg) return;
+  const uint64_t s0 = s * L, s1 = s0 + L < len ? s0 + L : len;
+  uint64_t row = s ? ends[s - 1] : 0, prev = s ? last[s - 1] : 0;
+  const uint64_t row_end = ends[s];
+  for (uint64_t w = s0 >> 5; w <= (s1 - 1) >> 5; w++) {
+    uint32_t m = cur[w];
+    while (m && row < row_end) {
+      const uint64_t end = (w << 5) + (uint64_t)__ffs((int)m);  // bit k set: ends after byte w * 32 + k
+      m &= m - 1;
+      offsets[row] = prev;
+      sizes[row] = (uint32_t)(end - prev);
+      prev = end;
+      row++;
+    }
+  }
+}
+
+std::atomic<uint64_t> g_last_stats[4];  // sf_test_zpaq_device_stats
+
+inline uint64_t gcd64(uint64_t a, uint64_t b) {
+  while (b) {
+    const uint64_t t = a % b;
+    a = b;
+    b = t;
+  }
+  return a;
+}
+
+inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+}  // namespace
+
+namespace sfi {
+
+uint64_t zpaq_segment_len(uint32_t max_size) { return (uint64_t)max_size / gcd64(max_size, 32) * 32; }
+
+int zpaq_check_device_params(uint32_t bits, uint32_t max_size) {
+  return bits >= 1 && bits <= 31 && max_size >= kMinMaxSize && max_size <= kMaxMaxSize ? SF_OK : SF_EINVAL;
+}
+
+// The cut of d_data[0, len) (len > 0) up to the count: everything but the
+// rows.  Blocking (one synchronisation of `s` per join round and one for the
+// count).  The plan holds stream-ordered scratch until zpaq_cut_free.
+int zpaq_cut_plan(const uint8_t* d_data, uint64_t len, uint32_t bits, uint32_t max_size, hipStream_t s, ZpaqPlan* p) {
+  *p = ZpaqPlan{};
+  const uint64_t L = zpaq_segment_len(max_size), nseg = ceil_div(len, L), nwords = ceil_div(len, 32);
+  if (ceil_div(nseg, kLanes) > 0x7FFFFFFFull) return SF_EINVAL;
+  size_t tmp = 0;
+  uint64_t* nul = nullptr;
+  if (rocprim::inclusive_scan(nullptr, tmp, nul, nul, (size_t)nseg, rocprim::plus<uint64_t>(), s) != hipSuccess) {
+    (void)hipGetLastError();
+    return SF_ENODEV;
+  }
+  const size_t wb = align256(nwords * 4), sb = align256(nseg * 8);
+  uint8_t* ws = nullptr;
+  const int arc = stream_alloc(reinterpret_cast<void**>(&ws), 2 * wb + 7 * sb + 256 + tmp + 8, s);
+  if (arc != SF_OK) return arc;
+  p->ws = ws;
+  uint32_t* spec = reinterpret_cast<uint32_t*>(ws);
+  uint32_t* cur = reinterpret_cast<uint32_t*>(ws + wb);
+  uint64_t* seg = reinterpret_cast<uint64_t*>(ws + 2 * wb);
+  const size_t sw = sb / 8;
+  uint64_t *last[2] = {seg, seg + sw}, *lastspec = seg + 2 * sw, *used = seg + 3 * sw, *counts = seg + 4 * sw,
+           *ends = seg + 5 * sw;
+  Counters* ctr = reinterpret_cast<Counters*>(ws + 2 * wb + 7 * sb);
+  void* scan_tmp = ws + 2 * wb + 7 * sb + 256;
+  const uint32_t lim = sfz::limit(bits);
+  const dim3 grid((unsigned)ceil_div(nseg, kLanes)), block(kLanes);
+  SF_HIP(hipMemsetAsync(ctr, 0, sizeof(Counters), s));
+  clear_stale_error();
+  hipLaunchKernelGGL(zpaq_round0_kernel, grid, block, 0, s, d_data, len, L, nseg, lim, max_size, spec, cur, last[0],
+                     lastspec, used);
+  SF_HIP(hipGetLastError());
+  uint64_t rounds = 0;
+  int in = 0;
+  Counters hc{};
+  for (; nseg > 1; rounds++) {
+    if (rounds > nseg) return SF_EIO;  // cannot happen: the fixed point is reached in nseg rounds
+    SF_HIP(hipMemsetAsync(&ctr->changed, 0, sizeof(uint32_t), s));
+    clear_stale_error();
+    hipLaunchKernelGGL(zpaq_join_kernel, grid, block, 0, s, d_data, len, L, nseg, lim, max_size, spec, cur, last[in],
+                       last[in ^ 1], lastspec, used, ctr);
+    SF_HIP(hipGetLastError());
+    SF_HIP(hipMemcpyAsync(&hc, ctr, sizeof(Counters), hipMemcpyDeviceToHost, s));
+    SF_HIP(hipStreamSynchronize(s));
+    in ^= 1;
+    if (hc.changed == 0) break;
+  }
+  const dim3 g256((unsigned)ceil_div(nseg, 256));
+  clear_stale_error();
+  hipLaunchKernelGGL(zpaq_count_kernel, g256, dim3(256), 0, s, cur, len, L, nseg, counts);
+  SF_HIP(hipGetLastError());
+  if (rocprim::inclusive_scan(scan_tmp, tmp, counts, ends, (size_t)nseg, rocprim::plus<uint64_t>(), s) != hipSuccess) {
+    (void)hipGetLastError();
+    return SF_ENODEV;
+  }
+  uint64_t total = 0;
+  SF_HIP(hipMemcpyAsync(&total, ends + nseg - 1, 8, hipMemcpyDeviceToHost, s));
+  SF_HIP(hipStreamSynchronize(s));
+  p->len = len;
+  p->L = L;
+  p->nseg = nseg;
+  p->total = total;
+  p->cur = cur;
+  p->ends = ends;
+  p->last = last[in];
+  g_last_stats[0].store(L, std::memory_order_relaxed);
+  g_last_stats[1].store(nseg, std::memory_order_relaxed);
+  g_last_stats[2].store(rounds, std::memory_order_relaxed);
+  g_last_stats[3].store(hc.recut, std::memory_order_relaxed);
+  return SF_OK;
+}
+
+// The rows of a plan: p.total entries at d_offsets / d_sizes.  Asynchronous.
+int zpaq_cut_emit(const ZpaqPlan& p, uint64_t* d_offsets, uint32_t* d_sizes, hipStream_t s) {
+  clear_stale_error();
+  hipLaunchKernelGGL(zpaq_emit_kernel, dim3((unsigned)ceil_div(p.nseg, 256)), dim3(256), 0, s,
+                     static_cast<const uint32_t*>(p.cur), p.len, p.L, p.nseg, static_cast<const uint64_t*>(p.ends),
+                     static_cast<const uint64_t*>(p.last), d_offsets, d_sizes);
+  return hip_err(hipGetLastError());
+}
+
+void zpaq_cut_free(ZpaqPlan* p, hipStream_t s) {
+  stream_free(p->ws, s);
+  p->ws = nullptr;
+}
+
+}  // namespace sfi
+
+using namespace sfi;
+
+namespace {
+
+// A plan's scratch goes back on every path out of a call.
+struct PlanGuard {
+  ZpaqPlan p;
+  hipStream_t s;
+  ~PlanGuard() { zpaq_cut_free(&p, s); }
+};
+
+int cut_device(const void* d_data, uint64_t len, uint32_t bits, uint32_t max_size, uint64_t* d_offsets,
+               uint32_t* d_sizes, uint64_t cap_blocks, uint64_t* n_blocks, hipStream_t s) {
+  if (n_blocks) *n_blocks = 0;
+  if (!n_blocks || zpaq_check_device_params(bits, max_size) != SF_OK) return SF_EINVAL;
+  if (len == 0) return SF_OK;
+  if (!d_data) return SF_EINVAL;
+  PlanGuard g{{}, s};
+  int rc = zpaq_cut_plan(static_cast<const uint8_t*>(d_data), len, bits, max_size, s, &g.p);
+  if (rc != SF_OK) return rc;
+  *n_blocks = g.p.total;
+  if (g.p.total > cap_blocks || !d_offsets || !d_sizes) return SF_ENOSPC;
+  return zpaq_cut_emit(g.p, d_offsets, d_sizes, s);
+}
+
+const uint8_t* pread_all(int fd, uint64_t pos, uint64_t want, uint8_t* buf) {
+  for (uint64_t got = 0; got < want;) {
+    const ssize_t r = pread(fd, buf + got, want - got, (off_t)(pos + got));
+    if (r < 0 && errno == EINTR) continue;
+    if (r <= 0) return nullptr;  // an error, or the file shrank
+    got += (uint64_t)r;
+  }
+  return buf;
+}
+
+constexpr uint64_t kFdPiece = 4ull << 20;  // bytes a reader thread reads, then copies to HBM, at a time
+
+int index_fd_zpaq_body(int fd, const sf_file_stamp* expect, uint32_t bits, uint32_t max_size, sf_block_sig** rows,
+                       uint64_t* n_out, uint8_t* blocks_hash) {
+  if (rows) *rows = nullptr;
+  if (n_out) *n_out = 0;
+  if (fd < 0 || !rows || !n_out || !blocks_hash || zpaq_check_device_params(bits, max_size) != SF_OK)
+    return SF_EINVAL;
+  sf_file_stamp before{}, after{};
+  mode_t mode = 0;
+  if (!stamp_of(fd, &before, &mode)) return SF_EIO;
+  if (!S_ISREG(mode)) return SF_EINVAL;
+  if (expect && !same_stamp(before, *expect)) return SF_EAGAIN;
+  const uint64_t len = before.size;
+  std::vector<sf_block_sig> rows_v;
+  sf_host_sha1_stream bh;
+  sf_host_sha1_begin(&bh);
+  if (len) {
+    int dev = 0;
+    SF_HIP(hipGetDevice(&dev));
+    // a window holds at least two chunks, so dropping its last one leaves one
+    const int64_t wk = knob(K_TEST_ZPAQ_WINDOW);
+    const uint64_t W = std::max<uint64_t>(wk > 0 ? (uint64_t)wk : kCacheMax, 2ull * max_size);
+    HostLease res;
+    hipStream_t* st;
+    hipEvent_t* ev;
+    uint8_t *pin = nullptr, *dwin = nullptr;
+    const uint64_t wbytes = std::min(len, W);
+    int rc = res.streams(st, ev);
+    if (rc == SF_OK) rc = res.pin(0, wbytes, reinterpret_cast<void**>(&pin));
+    if (rc == SF_OK) rc = res.dev(0, wbytes, reinterpret_cast<void**>(&dwin));
+    if (rc != SF_OK) return rc;
+    hipStream_t s = st[0];
+    uint64_t w = 0;
+    for (uint64_t A = 0; A < len; w++) {
+      const uint64_t B = std::min(len, A + W), n_bytes = B - A;
+      const bool eof = B == len;
+      // the window, read once: each reader thread takes pieces, and a piece's
+      // copy to HBM starts as soon as it is in the pinned window
+      const uint64_t pieces = ceil_div(n_bytes, kFdPiece);
+      std::atomic<uint64_t> next{0};
+      std::atomic<int> fail{SF_OK};
+      run_pool((unsigned)std::min<uint64_t>(io_threads(), pieces), [&] {
+        if (hipSetDevice(dev) != hipSuccess) {
+          (void)hipGetLastError();
+          fail.store(SF_ENODEV);
+          return;
+        }
+        for (uint64_t k; (k = next.fetch_add(1)) < pieces;) {
+          const uint64_t o = k * kFdPiece, m = std::min(kFdPiece, n_bytes - o);
+          if (!pread_all(fd, A + o, m, pin + o)) {
+            fail.store(SF_EIO);
+            return;
+          }
+          if (hipMemcpyAsync(dwin + o, pin + o, m, hipMemcpyHostToDevice, s) != hipSuccess) {
+            (void)hipGetLastError();
+            fail.store(SF_ENODEV);
+            return;
+          }
+        }
+      });
+      rc = fail.load();
+      read_hook(w);
+      if (rc == SF_EIO && stamp_of(fd, &after, nullptr) && !same_stamp(before, after)) rc = SF_EAGAIN;
+      if (rc != SF_OK) return rc;
+      PlanGuard g{{}, s};
+      if ((rc = zpaq_cut_plan(dwin, n_bytes, bits, max_size, s, &g.p)) != SF_OK) return rc;
+      // a non-final window's last block was closed by the window's end, not by
+      // the chunker: it is dropped, and the next window starts at its offset
+      // (a true cut)
+      const uint64_t n = g.p.total, keep = eof ? n : n - 1;
+      uint8_t *plist = nullptr, *dlist = nullptr, *pdig = nullptr, *ddig = nullptr;
+      const uint64_t lbytes = n * (sizeof(uint64_t) + sizeof(uint32_t));
+      if ((rc = res.pin(5, lbytes, reinterpret_cast<void**>(&plist))) != SF_OK ||
+          (rc = res.dev(5, lbytes, reinterpret_cast<void**>(&dlist))) != SF_OK ||
+          (rc = res.pin(3, n * 20, reinterpret_cast<void**>(&pdig))) != SF_OK ||
+          (rc = res.dev(3, n * 20, reinterpret_cast<void**>(&ddig))) != SF_OK)
+        return rc;
+      uint64_t* d_off = reinterpret_cast<uint64_t*>(dlist);
+      uint32_t* d_sz = reinterpret_cast<uint32_t*>(d_off + n);
+      if ((rc = zpaq_cut_emit(g.p, d_off, d_sz, s)) != SF_OK) return rc;
+      if (keep && (rc = launch_table(dwin, n_bytes, d_off, d_sz, keep, ddig, nullptr, s)) != SF_OK) return rc;
+      SF_HIP(hipMemcpyAsync(plist, dlist, lbytes, hipMemcpyDeviceToHost, s));
+      if (keep) SF_HIP(hipMemcpyAsync(pdig, ddig, keep * 20, hipMemcpyDeviceToHost, s));
+      SF_HIP(hipStreamSynchronize(s));
+      const uint64_t* lo = reinterpret_cast<const uint64_t*>(plist);
+      const uint32_t* lz = reinterpret_cast<const uint32_t*>(lo + n);
+      const size_t r0 = rows_v.size();
+      rows_v.resize(r0 + keep);
+      for (uint64_t j = 0; j < keep; j++) {
+        rows_v[r0 + j].offset = A + lo[j];
+        rows_v[r0 + j].size = lz[j];
+        memcpy(rows_v[r0 + j].sha1, pdig + 20 * j, 20);
+      }
+      sf_host_sha1_update(&bh, pdig, keep * 20);  // compute_blocks_hash (src/index.rs:661-682), in order
+      if (eof) break;
+      if (keep == 0) return SF_EIO;  // cannot happen: W >= 2 * max_size
+      A += lo[n - 1];
+    }
+    if (!stamp_of(fd, &after, nullptr)) return SF_EIO;
+    if (!same_stamp(before, after)) return SF_EAGAIN;  // written while read: not one version's rows
+  }
+  sf_block_sig* out = static_cast<sf_block_sig*>(malloc((rows_v.empty() ? 1 : rows_v.size()) * sizeof(sf_block_sig)));
+  if (!out) return SF_ENOMEM;
+  if (!rows_v.empty()) memcpy(out, rows_v.data(), rows_v.size() * sizeof(sf_block_sig));
+  sf_host_sha1_final(&bh, blocks_hash);
+  *rows = out;
+  *n_out = rows_v.size();
+  return SF_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sf_cut_device_zpaq(const void* d_data, uint64_t len, uint32_t bits, uint32_t max_size, uint64_t* d_offsets,
+                       uint32_t* d_sizes, uint64_t cap_blocks, uint64_t* n_blocks, void* stream) {
+  return guarded(
+      [&] { return cut_device(d_data, len, bits, max_size, d_offsets, d_sizes, cap_blocks, n_blocks, as_stream(stream)); });
+}
+
+int sf_index_device_zpaq(const void* d_data, uint64_t len, uint32_t bits, uint32_t max_size, uint64_t* d_offsets,
+                         uint32_t* d_sizes, void* d_digests, uint64_t cap_blocks, uint64_t* n_blocks,
+                         uint8_t* blocks_hash, void* stream) {
+  return guarded([&]() -> int {
+    hipStream_t s = as_stream(stream);
+    int rc = cut_device(d_data, len, bits, max_size, d_offsets, d_sizes, cap_blocks, n_blocks, s);
+    if (rc != SF_OK) return rc;
+    const uint64_t n = *n_blocks;
+    if (n && !d_digests) return SF_EINVAL;
+    if (n && (rc = launch_table(d_data, len, d_offsets, d_sizes, n, d_digests, nullptr, s)) != SF_OK) return rc;
+    if (!blocks_hash) return SF_OK;
+    std::vector<uint8_t> dig(n * 20);
+    if (n) {
+      SF_HIP(hipMemcpyAsync(dig.data(), d_digests, n * 20, hipMemcpyDeviceToHost, s));
+      SF_HIP(hipStreamSynchronize(s));
+    }
+    return sf_blocks_hash(dig.data(), n, blocks_hash);
+  });
+}
+
+int sf_index_fd_zpaq(int fd, const sf_file_stamp* expect, uint32_t bits, uint32_t max_size, sf_block_sig** rows,
+                     uint64_t* n_out, uint8_t blocks_hash[SF_HASH_DIGEST_LEN]) {
+  return guarded([&] { return index_fd_zpaq_body(fd, expect, bits, max_size, rows, n_out, blocks_hash); });
+}
+
+int sf_test_zpaq_device_stats(uint64_t out[4]) {
+  if (!out) return SF_EINVAL;
+  for (int k = 0; k < 4; k++) out[k] = g_last_stats[k].load(std::memory_order_relaxed);
+  return SF_OK;
+}
+
+}  // extern "C"

@@ -8,7 +8,9 @@
 //   sf_files.cpp  sf_index_files, the many-file pipeline;
 //   sf_fds.cpp    sf_index_fds_blocks, the default mode over many files;
 //   sf_multi.cpp  one process, N devices;
-//   sf_pool.cpp   the host worker threads of every pipeline (run_pool).
+//   sf_pool.cpp   the host worker threads of every pipeline (run_pool);
+//   sf_zpaq.cpp   the reference's ZPAQ chunker on the host;
+//   sf_cdc.hip    the same boundaries cut on the device (its own kernels).
 // The .cpp files use only the HIP runtime API (no kernels), so they build
 // with the host compiler.
 #pragma once
@@ -50,7 +52,7 @@ enum Knob {
   K_IO_THREADS, K_INPLACE_MIN_MIB, K_INPLACE_SERIAL, K_FADVISE, K_NO_HOSTREG, K_TABLE_CLASS_BITS, K_TRACE,
   K_BATCH_FUSED,
   K_TEST_INPLACE_FAIL_AT, K_TEST_WIRE_CHUNK, K_TEST_STREAM_STAGE_MIB, K_TEST_LAUNCH_MAX_BLOCKS, K_TEST_TABLE_SORT,
-  K_TEST_MULTI_SELF_GATHER, K_TEST_CUT_WINDOW_MIB, K_TEST_STREAM_POOL, K_COUNT
+  K_TEST_MULTI_SELF_GATHER, K_TEST_CUT_WINDOW_MIB, K_TEST_STREAM_POOL, K_TEST_ZPAQ_WINDOW, K_COUNT
 };
 struct KnobDef {
   const char* env;
@@ -309,5 +311,21 @@ int class_order(const uint32_t* d_sizes, uint64_t n, uint32_t mbits, uint32_t km
 int launch_table_kernel(bool weak_form, const uint8_t* d_data, uint64_t len, const uint64_t* d_offsets,
                         const uint32_t* d_sizes, uint64_t nblocks, uint8_t* d_digests, int* d_status, uint32_t* weak,
                         const uint32_t* order, hipStream_t stream);
+
+// The device ZPAQ cutter (sf_cdc.hip): a plan is the cut of one buffer up to
+// its block count (blocking: a synchronisation per join round and one for the
+// count), zpaq_cut_emit writes its `total` rows (asynchronous), zpaq_cut_free
+// gives its stream-ordered scratch back.  zpaq_segment_len: the segment
+// length, a function of max_size only.
+struct ZpaqPlan {
+  void* ws = nullptr;
+  uint64_t len = 0, L = 0, nseg = 0, total = 0;
+  const void *cur = nullptr, *ends = nullptr, *last = nullptr;
+};
+uint64_t zpaq_segment_len(uint32_t max_size);
+int zpaq_check_device_params(uint32_t bits, uint32_t max_size);
+int zpaq_cut_plan(const uint8_t* d_data, uint64_t len, uint32_t bits, uint32_t max_size, hipStream_t s, ZpaqPlan* p);
+int zpaq_cut_emit(const ZpaqPlan& p, uint64_t* d_offsets, uint32_t* d_sizes, hipStream_t s);
+void zpaq_cut_free(ZpaqPlan* p, hipStream_t s);
 
 }  // namespace sfi

@@ -11,6 +11,9 @@ Reference mapping (/root/reference):
                            (the reference's CDC boundaries, src/index.rs:622-625)
   index_device_batch    -> index_path_rec over many files (src/index.rs:689-715)
                            + compute_blocks_hash per file (src/index.rs:661-682)
+  cut_device_zpaq       -> the reference's own chunker (cdchunking's ZPAQ,
+                           src/index.rs:622-625) cut on the device
+  index_device_zpaq     -> index_file's default mode end to end in HBM
 """
 from __future__ import annotations
 
@@ -27,6 +30,7 @@ __all__ = [
     "num_blocks", "index_device", "index_device_blocks", "index_device_batch",
     "index_device_weak", "index_device_blocks_weak", "BatchStream",
     "fill_splitmix", "splitmix_tensor", "BlockSet", "index_device_multi",
+    "cut_device_zpaq", "index_device_zpaq", "zpaq_segment_len", "zpaq_device_stats",
 ]
 
 
@@ -125,6 +129,71 @@ def index_device_blocks(data: torch.Tensor, offsets: torch.Tensor, sizes: torch.
     return out
 
 
+def zpaq_segment_len(max_size: int) -> int:
+    """Segment length of the device ZPAQ cutter: lcm(max_size, 32) bytes, a
+    function of max_size only (include/syncfast_amd.h, sf_cut_device_zpaq)."""
+    import math
+    return max_size // math.gcd(max_size, 32) * 32
+
+
+def zpaq_device_stats() -> Tuple[int, int, int, int]:
+    """(segment length, segments, join rounds, bytes cut again) of the most
+    recent device cut in this process (sf_test_zpaq_device_stats)."""
+    out = (ctypes.c_uint64 * 4)()
+    check(lib().sf_test_zpaq_device_stats(out), "sf_test_zpaq_device_stats")
+    return tuple(int(v) for v in out)
+
+
+def _zpaq_call(data, bits, max_size, stream, digests: bool, blocks_hash: bool):
+    """sf_cut_device_zpaq / sf_index_device_zpaq with outputs sized from a
+    guess (len >> (bits - 1) + 16 blocks) and once more from the need the
+    library reports with SF_ENOSPC."""
+    from ._lib import SF_ENOSPC
+    _require_device(data, "data", torch.uint8)
+    n = data.numel()
+    cap = min(n, (n >> max(bits - 1, 0)) + n // max_size + 16)
+    bh = (ctypes.c_uint8 * 20)() if blocks_hash else None
+    nb = ctypes.c_uint64(0)
+    with _on(data.device, stream):
+        for _attempt in range(2):
+            offs = torch.empty(cap, dtype=torch.int64, device=data.device)
+            sizes = torch.empty(cap, dtype=torch.int32, device=data.device)
+            dig = torch.empty((cap, 20), dtype=torch.uint8, device=data.device) if digests else None
+            args = (data.data_ptr() if n else None, n, bits, max_size, offs.data_ptr() if cap else None,
+                    sizes.data_ptr() if cap else None)
+            if digests:
+                rc = lib().sf_index_device_zpaq(*args, dig.data_ptr() if cap else None, cap, ctypes.byref(nb), bh,
+                                                _stream_ptr(data, stream))
+            else:
+                rc = lib().sf_cut_device_zpaq(*args, cap, ctypes.byref(nb), _stream_ptr(data, stream))
+            if rc != SF_ENOSPC:
+                break
+            cap = nb.value
+        check(rc, "sf_index_device_zpaq" if digests else "sf_cut_device_zpaq")
+    k = nb.value
+    return offs[:k], sizes[:k], (dig[:k] if digests else None), (bytes(bh) if blocks_hash else None)
+
+
+def cut_device_zpaq(data: torch.Tensor, bits: int = 13, max_size: int = 32768,
+                    stream: Optional[torch.cuda.Stream] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The reference's content-defined (ZPAQ) blocks of a uint8 HBM buffer, cut
+    on the device (sf_cut_device_zpaq): (offsets int64[n], sizes int32[n]) in
+    file order, exactly host.zpaq_cut_buffer's list -- what index_device_blocks
+    takes.  Blocking: the stream is synchronised once per join round."""
+    offs, sizes, _d, _h = _zpaq_call(data, bits, max_size, stream, False, False)
+    return offs, sizes
+
+
+def index_device_zpaq(data: torch.Tensor, bits: int = 13, max_size: int = 32768, blocks_hash: bool = True,
+                      stream: Optional[torch.cuda.Stream] = None):
+    """index_file's default mode (src/index.rs:621-656) for bytes already in
+    HBM (sf_index_device_zpaq): the cut, every block's SHA-1 and, with
+    ``blocks_hash``, the file's blocks_hash (bytes, chained on the host).
+    Returns (offsets int64[n], sizes int32[n], digests uint8[n, 20],
+    blocks_hash or None)."""
+    return _zpaq_call(data, bits, max_size, stream, True, blocks_hash)
+
+
 def index_device_weak(data: torch.Tensor, block_size: int, out: Optional[torch.Tensor] = None,
                       weak_out: Optional[torch.Tensor] = None, stream: Optional[torch.cuda.Stream] = None):
     """index_device plus the opt-in weak sum: (digests uint8[n, 20], weak
@@ -181,11 +250,13 @@ def index_device_batch(data: torch.Tensor, files: Sequence[Tuple[int, int]], blo
     ``files`` = [(offset, length), ...].  Returns (digests uint8[n,20],
     first_block int64[n_files+1], file_hashes uint8[n_files,20] or None).
 
-    An equal-size batch with file_hashes runs ONE fused launch in which no
-    wave waits (the chains' slices run on the waves that complete their
-    dependencies), so nothing can time out.  ``status``
-    (int32[1] on the device, may be None) is passed through and is never
-    written; it stays for callers of the round-5 interface."""
+    An equal-size batch with file_hashes is hashed in two column halves (two
+    launches: the first half of every file's blocks_hash chain runs beside
+    the second half's blocks) and a last launch for the chains' second half
+    (include/syncfast_amd.h, sf_index_device_batch): no wave
+    waits for another, so nothing can time out.  ``status`` (int32[1] on the
+    device, may be None) is passed through and is never written; it stays
+    for callers of the round-5 interface."""
     _require_device(data, "data", torch.uint8)
     nf = len(files)
     descs = (FileDesc * max(nf, 1))()

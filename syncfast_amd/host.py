@@ -304,6 +304,59 @@ def index_fd_cut(fd: int, ops, threads: int = 0, stamp: FileStamp = None) -> Tup
     return rows, bytes(bh)
 
 
+def zpaq_cut_buffer(data, bits: int = 13, max_size: int = 32768) -> Tuple[np.ndarray, np.ndarray]:
+    """The reference's content-defined (ZPAQ) blocks of bytes in host memory,
+    cut sequentially on this thread (sf_zpaq_cut_buffer, the library's
+    definition of the boundaries): (offsets uint64, sizes uint32)."""
+    a = _u8(data)
+    cap = max(16, a.size >> max(bits - 2, 0))
+    n = ctypes.c_uint64(0)
+    for _attempt in range(2):
+        offs, sizes = np.zeros(cap, np.uint64), np.zeros(cap, np.uint32)
+        rc = lib().sf_zpaq_cut_buffer(a.ctypes.data if a.size else None, a.size, bits, max_size, offs.ctypes.data,
+                                      sizes.ctypes.data, cap, ctypes.byref(n))
+        if rc != SF_ENOSPC:
+            break
+        cap = n.value
+    check(rc, "sf_zpaq_cut_buffer")
+    return offs[:n.value], sizes[:n.value]
+
+
+class ZpaqOps(ctypes.Structure):
+    """An sf_chunker_ops filled by sf_zpaq_chunker_ops: the reference's
+    chunker for sf_cut_fd / sf_index_fd_cut (``.address`` is what they take).
+    The parameters live in its ctx field; nothing to release."""
+    _fields_ = [("create", ctypes.c_void_p), ("next", ctypes.c_void_p), ("destroy", ctypes.c_void_p),
+                ("ctx", ctypes.c_void_p)]
+
+    def __init__(self, bits: int = 13, max_size: int = 32768):
+        super().__init__()
+        check(lib().sf_zpaq_chunker_ops(bits, max_size, ctypes.addressof(self)), "sf_zpaq_chunker_ops")
+
+    @property
+    def address(self) -> int:
+        return ctypes.addressof(self)
+
+
+def index_fd_zpaq(fd: int, bits: int = 13, max_size: int = 32768, stamp: FileStamp = None) -> Tuple[np.ndarray, bytes]:
+    """index_file in the default mode for the regular file open on fd with no
+    host chunker: read once, cut and hashed on the device by windows
+    (sf_index_fd_zpaq).  Returns (rows, blocks_hash); SfError(SF_EAGAIN) if
+    the file changed."""
+    p = ctypes.POINTER(BlockSig)()
+    n = ctypes.c_uint64(0)
+    bh = (ctypes.c_uint8 * 20)()
+    check(lib().sf_index_fd_zpaq(fd, ctypes.byref(stamp) if stamp is not None else None, bits, max_size,
+                                 ctypes.byref(p), ctypes.byref(n), bh), "sf_index_fd_zpaq")
+    try:
+        rows = np.zeros(n.value, SIG_DTYPE)
+        if n.value:
+            ctypes.memmove(rows.ctypes.data, p, n.value * SIG_DTYPE.itemsize)
+    finally:
+        lib().sf_free_rows(p)
+    return rows, bytes(bh)
+
+
 def shard_range(file_len: int, block_size: int, n_shards: int, shard: int) -> Tuple[int, int]:
     """sf_shard_range: (start, length) of shard `shard` of n_shards (the
     partition of the multi-device forms)."""

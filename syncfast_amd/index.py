@@ -11,9 +11,12 @@ SHA-1 kernel and the rows are inserted in one batch.
 
 Chunking -- an explicit choice, there is no default.  The reference cuts
 blocks with the third-party cdchunking 0.2.1 ZPAQ chunker (src/index.rs:
-622-625), whose recurrence is not available here (CDC parity
-unpinned).  ``index_file`` / ``index_path`` therefore need the chunker the
-caller chose when opening the index:
+622-625); ``ZpaqChunker()`` is that chunker, from the library (its recurrence
+reproduces the reference's known-answer test).  ``index_file``
+/ ``index_path`` need the chunker the caller chose when opening the index:
+  * ``ZpaqChunker(bits=13, max_size=32768)`` -- the reference's blocks with
+    nothing handed in: a NativeChunker over sf_zpaq_chunker_ops, on host
+    threads or (``device=True``) cut on the GPU;
   * ``BoundaryChunker(fn)`` -- the reference's mode: the boundary function is
     the host chunker (in a Rust drop-in, the cdchunking crate itself), so the
     blocks are the reference's by construction; every block's SHA-1 and the
@@ -212,6 +215,11 @@ class NativeChunker(BoundaryChunker):
         self.ops = int(ops)
         self.threads = threads
 
+    def index_fd(self, fd: int, threads: int, stamp):
+        """(rows, blocks_hash) of the regular file open on fd: cut on
+        ``threads`` threads and hashed from one read (sf_index_fd_cut)."""
+        return host.index_fd_cut(fd, self.ops, threads, stamp)
+
     def _sizes(self, f) -> List[int]:
         if hasattr(f, "fileno"):
             try:
@@ -245,6 +253,30 @@ class NativeChunker(BoundaryChunker):
             return sizes
         finally:
             ops.destroy(ch)
+
+
+class ZpaqChunker(NativeChunker):
+    """The reference's own chunker (cdchunking's ZPAQ, src/index.rs:622-625:
+    13 bits, 32 KiB cap), from the library: a NativeChunker over
+    sf_zpaq_chunker_ops, so Index.index_file / index_path produce the
+    reference's blocks with no chunker handed in.  ``device=True`` cuts on
+    the GPU as well: Index.index_file, and index_path's large-file route, go
+    through sf_index_fd_zpaq (the file read once, cut and hashed in HBM by
+    windows) instead of sf_index_fd_cut's host threads; the rows are the
+    same.  The default stays on the host route: it is the faster one up to
+    about 1 GiB (DESIGN.md 3.7 has the measurements)."""
+
+    def __init__(self, bits: int = 13, max_size: int = 32768, device: bool = False, threads: int = 0):
+        self._zops = host.ZpaqOps(bits, max_size)  # kept alive: ops is its address
+        super().__init__(self._zops.address, threads)
+        self.bits, self.max_size, self.device = bits, max_size, device
+
+    def index_fd(self, fd: int, threads: int, stamp):
+        """(rows, blocks_hash) of the regular file open on fd, cut and hashed
+        in one call on the route this chunker was opened with."""
+        if self.device:
+            return host.index_fd_zpaq(fd, self.bits, self.max_size, stamp)
+        return host.index_fd_cut(fd, self.ops, threads, stamp)
 
 
 def _sizes_ok(sizes, n: int) -> List[int]:
@@ -586,7 +618,7 @@ class Index:
                 else:  # a FIFO: read sequentially from this open, as File::open + read do
                     native = host.index_fd(f.fileno(), ch.block_size)
             elif isinstance(ch, NativeChunker) and seekable and not one_pass:
-                native = host.index_fd_cut(f.fileno(), ch.ops, ch.threads, stamp)  # cut + hash, one read
+                native = ch.index_fd(f.fileno(), ch.threads, stamp)  # cut + hash, one read
             elif ch.stream and seekable and not one_pass:
                 sizes = [int(x) for x in ch.fn(f)]
                 if sum(sizes) != stamp.size and _stamp_moved(f.fileno(), stamp):
@@ -793,7 +825,7 @@ class Index:
                     if not up_to_date and native and stamp.size >= large_file_bytes > 0:
                         drain()
                         try:  # cut on the chunker's threads + hashed, one read of this open
-                            rows_np, bh = host.index_fd_cut(f.fileno(), ch.ops, ch.threads or threads, stamp)
+                            rows_np, bh = ch.index_fd(f.fileno(), ch.threads or threads, stamp)
                         except SfError as e:
                             if e.code != SF_EAGAIN:
                                 raise
