@@ -53,7 +53,6 @@
 #include <string.h>
 #include <sys/stat.h>
 #include <unistd.h>
-#include <errno.h>
 
 #include <rocprim/device/device_scan.hpp>
 
@@ -61,6 +60,7 @@
 
 #include "host_sha1.h"
 #include "sf_internal.hpp"
+#include "sf_stage.hpp"
 #include "sf_zpaq_step.hpp"
 #include "../../include/syncfast_amd_test.h"
 
@@ -455,17 +455,80 @@ int cut_device(const void* d_data, uint64_t len, uint32_t bits, uint32_t max_siz
   return zpaq_cut_emit(g.p, d_offsets, d_sizes, s);
 }
 
-const uint8_t* pread_all(int fd, uint64_t pos, uint64_t want, uint8_t* buf) {
-  for (uint64_t got = 0; got < want;) {
-    const ssize_t r = pread(fd, buf + got, want - got, (off_t)(pos + got));
-    if (r < 0 && errno == EINTR) continue;
-    if (r <= 0) return nullptr;  // an error, or the file shrank
-    got += (uint64_t)r;
-  }
-  return buf;
-}
-
 constexpr uint64_t kFdPiece = 4ull << 20;  // bytes a reader thread reads, then copies to HBM, at a time
+
+// The windows of sf_index_fd_zpaq over the `len` bytes of the regular file open
+// on fd: the rows into rb, folded into bh.
+int fd_zpaq_windows(int fd, uint64_t len, uint32_t bits, uint32_t max_size, RowBuf& rb, sf_host_sha1_stream* bh) {
+  int dev = 0;
+  SF_HIP(hipGetDevice(&dev));
+  // a window holds at least two chunks, so dropping its last one leaves one
+  const int64_t wk = knob(K_TEST_ZPAQ_WINDOW);
+  const uint64_t W = std::max<uint64_t>(wk > 0 ? (uint64_t)wk : kCacheMax, 2ull * max_size);
+  HostLease res;
+  hipStream_t* st;
+  hipEvent_t* ev;
+  uint8_t *pin = nullptr, *dwin = nullptr;
+  const uint64_t wbytes = std::min(len, W);
+  int rc = res.streams(st, ev);
+  if (rc == SF_OK) rc = res.pin(kSlotData, wbytes, reinterpret_cast<void**>(&pin));
+  if (rc == SF_OK) rc = res.dev(kSlotData, wbytes, reinterpret_cast<void**>(&dwin));
+  if (rc != SF_OK) return rc;
+  hipStream_t s = st[0];
+  uint64_t w = 0;
+  for (uint64_t A = 0; A < len; w++) {
+    const uint64_t B = std::min(len, A + W), n_bytes = B - A;
+    const bool eof = B == len;
+    // the window, read once: each reader thread takes pieces, and a piece's
+    // copy to HBM starts as soon as it is in the pinned window
+    const uint64_t pieces = ceil_div(n_bytes, kFdPiece);
+    std::atomic<uint64_t> next{0};
+    std::atomic<int> fail{SF_OK};
+    run_pool((unsigned)std::min<uint64_t>(io_threads(), pieces), [&] {
+      if (hipSetDevice(dev) != hipSuccess) {
+        (void)hipGetLastError();
+        fail.store(SF_ENODEV);
+        return;
+      }
+      for (uint64_t k; (k = next.fetch_add(1)) < pieces;) {
+        const uint64_t o = k * kFdPiece, m = std::min(kFdPiece, n_bytes - o);
+        if (!read_fully(fd, pin + o, A + o, m)) {  // an error, or the file shrank
+          fail.store(SF_EIO);
+          return;
+        }
+        if (hipMemcpyAsync(dwin + o, pin + o, m, hipMemcpyHostToDevice, s) != hipSuccess) {
+          (void)hipGetLastError();
+          fail.store(SF_ENODEV);
+          return;
+        }
+      }
+    });
+    rc = fail.load();
+    read_hook(w);
+    if (rc != SF_OK) return rc;
+    PlanGuard g{{}, s};
+    if ((rc = zpaq_cut_plan(dwin, n_bytes, bits, max_size, s, &g.p)) != SF_OK) return rc;
+    // a non-final window's last block was closed by the window's end, not by
+    // the chunker: it is dropped, and the next window starts at its offset
+    // (a true cut)
+    const uint64_t n = g.p.total, keep = eof ? n : n - 1;
+    const uint64_t lbytes = n * kListEntry;
+    StageBufs sb;
+    if ((rc = stage_bufs(res, 0, kNoBuf, n, lbytes, &sb)) != SF_OK) return rc;
+    uint64_t* d_off = static_cast<uint64_t*>(sb.daux);
+    uint32_t* d_sz = reinterpret_cast<uint32_t*>(d_off + n);
+    if ((rc = zpaq_cut_emit(g.p, d_off, d_sz, s)) != SF_OK) return rc;
+    if (keep && (rc = launch_table(dwin, n_bytes, d_off, d_sz, keep, sb.ddig, nullptr, s)) != SF_OK) return rc;
+    SF_HIP(hipMemcpyAsync(sb.paux, sb.daux, lbytes, hipMemcpyDeviceToHost, s));
+    if (keep) SF_HIP(hipMemcpyAsync(sb.pdig, sb.ddig, keep * 20, hipMemcpyDeviceToHost, s));
+    SF_HIP(hipStreamSynchronize(s));
+    if (!append_window_rows(rb, A, sb.paux, sb.pdig, n, keep, bh)) return SF_ENOMEM;
+    if (eof) break;
+    if (keep == 0) return SF_EIO;  // cannot happen: W >= 2 * max_size
+    A += static_cast<const uint64_t*>(sb.paux)[n - 1];
+  }
+  return SF_OK;
+}
 
 int index_fd_zpaq_body(int fd, const sf_file_stamp* expect, uint32_t bits, uint32_t max_size, sf_block_sig** rows,
                        uint64_t* n_out, uint8_t* blocks_hash) {
@@ -473,106 +536,19 @@ int index_fd_zpaq_body(int fd, const sf_file_stamp* expect, uint32_t bits, uint3
   if (n_out) *n_out = 0;
   if (fd < 0 || !rows || !n_out || !blocks_hash || zpaq_check_device_params(bits, max_size) != SF_OK)
     return SF_EINVAL;
-  sf_file_stamp before{}, after{};
-  mode_t mode = 0;
-  if (!stamp_of(fd, &before, &mode)) return SF_EIO;
-  if (!S_ISREG(mode)) return SF_EINVAL;
-  if (expect && !same_stamp(before, *expect)) return SF_EAGAIN;
-  const uint64_t len = before.size;
-  std::vector<sf_block_sig> rows_v;
+  RowBuf rb;
   sf_host_sha1_stream bh;
   sf_host_sha1_begin(&bh);
-  if (len) {
-    int dev = 0;
-    SF_HIP(hipGetDevice(&dev));
-    // a window holds at least two chunks, so dropping its last one leaves one
-    const int64_t wk = knob(K_TEST_ZPAQ_WINDOW);
-    const uint64_t W = std::max<uint64_t>(wk > 0 ? (uint64_t)wk : kCacheMax, 2ull * max_size);
-    HostLease res;
-    hipStream_t* st;
-    hipEvent_t* ev;
-    uint8_t *pin = nullptr, *dwin = nullptr;
-    const uint64_t wbytes = std::min(len, W);
-    int rc = res.streams(st, ev);
-    if (rc == SF_OK) rc = res.pin(0, wbytes, reinterpret_cast<void**>(&pin));
-    if (rc == SF_OK) rc = res.dev(0, wbytes, reinterpret_cast<void**>(&dwin));
-    if (rc != SF_OK) return rc;
-    hipStream_t s = st[0];
-    uint64_t w = 0;
-    for (uint64_t A = 0; A < len; w++) {
-      const uint64_t B = std::min(len, A + W), n_bytes = B - A;
-      const bool eof = B == len;
-      // the window, read once: each reader thread takes pieces, and a piece's
-      // copy to HBM starts as soon as it is in the pinned window
-      const uint64_t pieces = ceil_div(n_bytes, kFdPiece);
-      std::atomic<uint64_t> next{0};
-      std::atomic<int> fail{SF_OK};
-      run_pool((unsigned)std::min<uint64_t>(io_threads(), pieces), [&] {
-        if (hipSetDevice(dev) != hipSuccess) {
-          (void)hipGetLastError();
-          fail.store(SF_ENODEV);
-          return;
-        }
-        for (uint64_t k; (k = next.fetch_add(1)) < pieces;) {
-          const uint64_t o = k * kFdPiece, m = std::min(kFdPiece, n_bytes - o);
-          if (!pread_all(fd, A + o, m, pin + o)) {
-            fail.store(SF_EIO);
-            return;
-          }
-          if (hipMemcpyAsync(dwin + o, pin + o, m, hipMemcpyHostToDevice, s) != hipSuccess) {
-            (void)hipGetLastError();
-            fail.store(SF_ENODEV);
-            return;
-          }
-        }
-      });
-      rc = fail.load();
-      read_hook(w);
-      if (rc == SF_EIO && stamp_of(fd, &after, nullptr) && !same_stamp(before, after)) rc = SF_EAGAIN;
-      if (rc != SF_OK) return rc;
-      PlanGuard g{{}, s};
-      if ((rc = zpaq_cut_plan(dwin, n_bytes, bits, max_size, s, &g.p)) != SF_OK) return rc;
-      // a non-final window's last block was closed by the window's end, not by
-      // the chunker: it is dropped, and the next window starts at its offset
-      // (a true cut)
-      const uint64_t n = g.p.total, keep = eof ? n : n - 1;
-      uint8_t *plist = nullptr, *dlist = nullptr, *pdig = nullptr, *ddig = nullptr;
-      const uint64_t lbytes = n * (sizeof(uint64_t) + sizeof(uint32_t));
-      if ((rc = res.pin(5, lbytes, reinterpret_cast<void**>(&plist))) != SF_OK ||
-          (rc = res.dev(5, lbytes, reinterpret_cast<void**>(&dlist))) != SF_OK ||
-          (rc = res.pin(3, n * 20, reinterpret_cast<void**>(&pdig))) != SF_OK ||
-          (rc = res.dev(3, n * 20, reinterpret_cast<void**>(&ddig))) != SF_OK)
-        return rc;
-      uint64_t* d_off = reinterpret_cast<uint64_t*>(dlist);
-      uint32_t* d_sz = reinterpret_cast<uint32_t*>(d_off + n);
-      if ((rc = zpaq_cut_emit(g.p, d_off, d_sz, s)) != SF_OK) return rc;
-      if (keep && (rc = launch_table(dwin, n_bytes, d_off, d_sz, keep, ddig, nullptr, s)) != SF_OK) return rc;
-      SF_HIP(hipMemcpyAsync(plist, dlist, lbytes, hipMemcpyDeviceToHost, s));
-      if (keep) SF_HIP(hipMemcpyAsync(pdig, ddig, keep * 20, hipMemcpyDeviceToHost, s));
-      SF_HIP(hipStreamSynchronize(s));
-      const uint64_t* lo = reinterpret_cast<const uint64_t*>(plist);
-      const uint32_t* lz = reinterpret_cast<const uint32_t*>(lo + n);
-      const size_t r0 = rows_v.size();
-      rows_v.resize(r0 + keep);
-      for (uint64_t j = 0; j < keep; j++) {
-        rows_v[r0 + j].offset = A + lo[j];
-        rows_v[r0 + j].size = lz[j];
-        memcpy(rows_v[r0 + j].sha1, pdig + 20 * j, 20);
-      }
-      sf_host_sha1_update(&bh, pdig, keep * 20);  // compute_blocks_hash (src/index.rs:661-682), in order
-      if (eof) break;
-      if (keep == 0) return SF_EIO;  // cannot happen: W >= 2 * max_size
-      A += lo[n - 1];
-    }
-    if (!stamp_of(fd, &after, nullptr)) return SF_EIO;
-    if (!same_stamp(before, after)) return SF_EAGAIN;  // written while read: not one version's rows
-  }
-  sf_block_sig* out = static_cast<sf_block_sig*>(malloc((rows_v.empty() ? 1 : rows_v.size()) * sizeof(sf_block_sig)));
-  if (!out) return SF_ENOMEM;
-  if (!rows_v.empty()) memcpy(out, rows_v.data(), rows_v.size() * sizeof(sf_block_sig));
+  // (rows that end while the file is written are not one version's rows: SF_EAGAIN)
+  const int rc = stamped(fd, expect, [&](const sf_file_stamp& before, mode_t mode) {
+    if (!S_ISREG(mode)) return SF_EINVAL;
+    return before.size ? fd_zpaq_windows(fd, before.size, bits, max_size, rb, &bh) : SF_OK;
+  });
+  if (rc != SF_OK) return rc;
+  if (!rb.grow(1)) return SF_ENOMEM;  // no rows: still a pointer that free() takes
   sf_host_sha1_final(&bh, blocks_hash);
-  *rows = out;
-  *n_out = rows_v.size();
+  *n_out = rb.n;
+  *rows = rb.release();
   return SF_OK;
 }
 

@@ -27,7 +27,6 @@
 // joined list is hashed from HBM (sha1_table_kernel) -- no second read of the
 // file.  A window keeps the chunks a boundary closes inside it, and the next
 // window starts at the last such boundary.
-#include <errno.h>
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
@@ -45,6 +44,7 @@
 
 #include "host_sha1.h"
 #include "sf_internal.hpp"
+#include "sf_stage.hpp"
 
 using namespace sfi;
 
@@ -69,13 +69,7 @@ struct Chunker {
 using Fetch = std::function<const uint8_t*(uint64_t pos, uint64_t want, uint8_t* buf)>;
 
 const uint8_t* pread_fetch(int fd, uint64_t pos, uint64_t want, uint8_t* buf) {
-  for (uint64_t got = 0; got < want;) {
-    const ssize_t r = pread(fd, buf + got, want - got, (off_t)(pos + got));
-    if (r < 0 && errno == EINTR) continue;
-    if (r <= 0) return nullptr;  // an error, or the file shrank below len
-    got += (uint64_t)r;
-  }
-  return buf;
+  return read_fully(fd, buf, pos, want) ? buf : nullptr;  // an error, or the file shrank below len
 }
 
 // Cuts bytes [start, len) with a fresh chunker (start is a chunk's first
@@ -206,21 +200,15 @@ static int sf_cut_fd_body(int fd, const sf_file_stamp* expect, const sf_chunker_
   if (n_blocks) *n_blocks = 0;
   if (fd < 0 || !ops || !ops->create || !ops->next || !ops->destroy || !offsets || !sizes || !n_blocks)
     return SF_EINVAL;
-  sf_file_stamp before{}, after{};
-  mode_t mode = 0;
-  if (!stamp_of(fd, &before, &mode)) return SF_EIO;
-  if (!S_ISREG(mode)) return SF_EINVAL;  // segments need offsets: a regular file
-  if (expect && !same_stamp(before, *expect)) return SF_EAGAIN;
-  const uint64_t len = before.size;
   std::vector<uint64_t> ends;  // the true chain: every chunk's end, in order
-  const Fetch fetch = [fd](uint64_t pos, uint64_t want, uint8_t* buf) { return pread_fetch(fd, pos, want, buf); };
-  const int rc = cut_joined(fetch, 0, len, true, ops, threads, [](uint64_t, uint64_t, uint64_t) { return SF_OK; }, ends);
-  if (rc != SF_OK) {
-    if (rc == SF_EIO && stamp_of(fd, &after, nullptr) && !same_stamp(before, after)) return SF_EAGAIN;
-    return rc;
-  }
-  if (!stamp_of(fd, &after, nullptr)) return SF_EIO;
-  if (!same_stamp(before, after)) return SF_EAGAIN;  // written while cut: not one version's boundaries
+  // (a cut that ends while the file is written is not one version's boundaries: SF_EAGAIN)
+  const int rc = stamped(fd, expect, [&](const sf_file_stamp& before, mode_t mode) {
+    if (!S_ISREG(mode)) return SF_EINVAL;  // segments need offsets: a regular file
+    const Fetch fetch = [fd](uint64_t pos, uint64_t want, uint8_t* buf) { return pread_fetch(fd, pos, want, buf); };
+    return cut_joined(fetch, 0, before.size, true, ops, threads, [](uint64_t, uint64_t, uint64_t) { return SF_OK; },
+                      ends);
+  });
+  if (rc != SF_OK) return rc;
   const uint64_t n = ends.size();
   uint64_t* o = static_cast<uint64_t*>(malloc((n ? n : 1) * sizeof(uint64_t)));
   uint32_t* z = static_cast<uint32_t*>(malloc((n ? n : 1) * sizeof(uint32_t)));
@@ -255,17 +243,13 @@ void sf_free_cuts(void* p) { free(p); }
 // (the host cache's largest buffer) and its copy in HBM.
 static constexpr uint64_t kFusedMax = 512ull << 20;
 
-static int sf_index_fd_cut_body(int fd, const sf_file_stamp* expect, const sf_chunker_ops* ops, uint32_t threads,
-                                sf_block_sig** rows, uint64_t* n_out, uint8_t* blocks_hash) {
-  if (rows) *rows = nullptr;
-  if (n_out) *n_out = 0;
-  if (fd < 0 || !ops || !ops->create || !ops->next || !ops->destroy || !rows || !n_out || !blocks_hash)
-    return SF_EINVAL;
-  sf_file_stamp before{}, after{};
-  mode_t mode = 0;
-  if (!stamp_of(fd, &before, &mode)) return SF_EIO;
-  if (!S_ISREG(mode)) return SF_EINVAL;
-  if (expect && !same_stamp(before, *expect)) return SF_EAGAIN;
+// The windows of sf_index_fd_cut over the regular file open on fd, whose
+// stamp the caller took (`before`: its size is the file's length): the rows
+// into rb, blocks_hash over their digests.
+static int fd_cut_windows(int fd, const sf_file_stamp& before, const sf_chunker_ops* ops, uint32_t threads, RowBuf& rb,
+                          uint8_t* blocks_hash) {
+  sf_host_sha1_stream bh;
+  sf_host_sha1_begin(&bh);
   const uint64_t len = before.size;
   const auto ts = std::chrono::steady_clock::now();  // setup (lease, streams, windows): traced apart
   int dev = 0;
@@ -281,11 +265,11 @@ static int sf_index_fd_cut_body(int fd, const sf_file_stamp* expect, const sf_ch
   uint8_t *pin = nullptr, *dwin[2] = {nullptr, nullptr};
   const uint64_t wbytes = std::min(len, W);
   int rc = res->streams(st, done_ev);
-  if (rc == SF_OK) rc = res->pin(0, wbytes, reinterpret_cast<void**>(&pin));
+  if (rc == SF_OK) rc = res->pin(kSlotData, wbytes, reinterpret_cast<void**>(&pin));
   // two device windows: window w + 1 is read and copied while window w's
   // chunks are hashed (its device work overlaps the next window's cutting)
-  if (rc == SF_OK) rc = res->dev(0, wbytes, reinterpret_cast<void**>(&dwin[0]));
-  if (rc == SF_OK && len > W) rc = res->dev(1, wbytes, reinterpret_cast<void**>(&dwin[1]));
+  if (rc == SF_OK) rc = res->dev(kSlotData, wbytes, reinterpret_cast<void**>(&dwin[0]));
+  if (rc == SF_OK && len > W) rc = res->dev(kSlotData + 1, wbytes, reinterpret_cast<void**>(&dwin[1]));
   if (rc != SF_OK) return rc;
   struct Ev {  // window w's copies to HBM are done (the pinned window may be refilled)
     hipEvent_t e = nullptr;
@@ -300,9 +284,6 @@ static int sf_index_fd_cut_body(int fd, const sf_file_stamp* expect, const sf_ch
   auto ms = [&] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
   double t_cut = 0, t_dev = 0, t_issue = 0;  // issue: list, buffers and the launch, enqueued
   double t_ph[4] = {0, 0, 0, 0};  // issue's parts (trace): buffers, list upload, launch, digests back
-  std::vector<sf_block_sig> rows_v;
-  sf_host_sha1_stream bh;
-  sf_host_sha1_begin(&bh);
   const uint64_t nseg_max = 4096;
   std::vector<std::atomic<int>> seg_in(nseg_max);
   std::vector<std::atomic<const void*>> seg_owner(nseg_max);  // the thread cutting segment i (its tl_me)
@@ -324,16 +305,7 @@ static int sf_index_fd_cut_body(int fd, const sf_file_stamp* expect, const sf_ch
     const double d0 = ms();
     SF_HIP(hipEventSynchronize(done_ev[w & 1]));
     t_dev += ms() - d0;
-    const uint64_t* lo = reinterpret_cast<const uint64_t*>(p.plist);
-    const uint32_t* lz = reinterpret_cast<const uint32_t*>(lo + p.n);
-    const size_t r0 = rows_v.size();
-    rows_v.resize(r0 + p.n);
-    for (uint64_t j = 0; j < p.n; j++) {
-      rows_v[r0 + j].offset = p.A + lo[j];
-      rows_v[r0 + j].size = lz[j];
-      memcpy(rows_v[r0 + j].sha1, p.pdig + 20 * j, 20);
-    }
-    sf_host_sha1_update(&bh, p.pdig, p.n * 20);  // compute_blocks_hash (src/index.rs:661-682), in order
+    if (!append_window_rows(rb, p.A, p.plist, p.pdig, p.n, p.n, &bh)) return SF_ENOMEM;
     p.on = false;
     return SF_OK;
   };
@@ -398,7 +370,6 @@ static int sf_index_fd_cut_body(int fd, const sf_file_stamp* expect, const sf_ch
     rc = len ? cut_joined(fetch, A, B, eof, ops, threads, seg_begin, ends, seg_end) : SF_OK;
     if (copy_failed.load(std::memory_order_relaxed)) rc = SF_ENODEV;
     t_cut += ms() - c0;
-    if (rc == SF_EIO && stamp_of(fd, &after, nullptr) && !same_stamp(before, after)) rc = SF_EAGAIN;
     if (rc != SF_OK) return rc;
     // the window's copies are queued on st[0]; the pinned window is refilled
     // only once they are done (below, before the next window's cut)
@@ -410,17 +381,11 @@ static int sf_index_fd_cut_body(int fd, const sf_file_stamp* expect, const sf_ch
       uint64_t *o = nullptr, n = 0;
       uint32_t* z = nullptr;
       if ((rc = sf_cut_fd_body(fd, &before, ops, threads, &o, &z, &n)) != SF_OK) return rc;
-      sf_block_sig* out = static_cast<sf_block_sig*>(malloc((n ? n : 1) * sizeof(sf_block_sig)));
-      rc = out ? sf_index_fd_blocks(fd, &before, o, z, n, out, blocks_hash) : SF_ENOMEM;
+      rc = rb.grow(std::max<uint64_t>(n, 1)) ? sf_index_fd_blocks(fd, &before, o, z, n, rb.p, blocks_hash) : SF_ENOMEM;
       free(o);
       free(z);
-      if (rc != SF_OK) {
-        free(out);
-        return rc;
-      }
-      *rows = out;
-      *n_out = n;
-      return SF_OK;
+      rb.n = n;
+      return rc;
     }
     // the previous window's rows (its device work ran during this cut)
     if (w > 0 && (rc = harvest(w - 1)) != SF_OK) return rc;
@@ -429,14 +394,12 @@ static int sf_index_fd_cut_body(int fd, const sf_file_stamp* expect, const sf_ch
     const uint64_t n = ends.size();
     const double i0 = ms();
     if (n) {
-      uint8_t *plist = nullptr, *dlist = nullptr, *pdig = nullptr, *ddig = nullptr;
-      const uint64_t lbytes = n * (sizeof(uint64_t) + sizeof(uint32_t));
+      const uint64_t lbytes = n * kListEntry;
       const int b = (int)(w & 1);
-      if ((rc = res->pin(5 + b, lbytes, reinterpret_cast<void**>(&plist))) != SF_OK ||
-          (rc = res->dev(5 + b, lbytes, reinterpret_cast<void**>(&dlist))) != SF_OK ||
-          (rc = res->pin(3 + b, n * 20, reinterpret_cast<void**>(&pdig))) != SF_OK ||
-          (rc = res->dev(3 + b, n * 20, reinterpret_cast<void**>(&ddig))) != SF_OK)
-        return rc;
+      StageBufs sb;
+      if ((rc = stage_bufs(*res, b, kNoBuf, n, lbytes, &sb)) != SF_OK) return rc;
+      uint8_t *plist = static_cast<uint8_t*>(sb.paux), *dlist = static_cast<uint8_t*>(sb.daux);
+      uint8_t *pdig = static_cast<uint8_t*>(sb.pdig), *ddig = static_cast<uint8_t*>(sb.ddig);
       const double p1 = ms();
       t_ph[0] += p1 - i0;
       uint64_t* lo = reinterpret_cast<uint64_t*>(plist);
@@ -477,21 +440,33 @@ static int sf_index_fd_cut_body(int fd, const sf_file_stamp* expect, const sf_ch
   const double h0 = ms();
   if ((rc = harvest(w)) != SF_OK) return rc;  // the last window
   const double t_last = ms() - h0;
-  if (!stamp_of(fd, &after, nullptr)) return SF_EIO;
-  if (!same_stamp(before, after)) return SF_EAGAIN;  // written while read: not one version's rows
   if (trace)
     fprintf(stderr,
             "sf_index_fd_cut trace: %llu B, %zu blocks, %llu windows: setup %.3f, cut+join %.3f, issue %.3f "
             "(buffers %.3f, list %.3f, launch %.3f, back %.3f), waits %.3f (last harvest %.3f), total %.3f ms "
             "(setup not included)\n",
-            (unsigned long long)len, rows_v.size(), (unsigned long long)(w + 1), t_setup, t_cut, t_issue, t_ph[0],
+            (unsigned long long)len, (size_t)rb.n, (unsigned long long)(w + 1), t_setup, t_cut, t_issue, t_ph[0],
             t_ph[1], t_ph[2], t_ph[3], t_dev, t_last, ms());
-  sf_block_sig* out = static_cast<sf_block_sig*>(malloc((rows_v.empty() ? 1 : rows_v.size()) * sizeof(sf_block_sig)));
-  if (!out) return SF_ENOMEM;
-  if (!rows_v.empty()) memcpy(out, rows_v.data(), rows_v.size() * sizeof(sf_block_sig));
   sf_host_sha1_final(&bh, blocks_hash);
-  *rows = out;
-  *n_out = rows_v.size();
+  return SF_OK;
+}
+
+static int sf_index_fd_cut_body(int fd, const sf_file_stamp* expect, const sf_chunker_ops* ops, uint32_t threads,
+                                sf_block_sig** rows, uint64_t* n_out, uint8_t* blocks_hash) {
+  if (rows) *rows = nullptr;
+  if (n_out) *n_out = 0;
+  if (fd < 0 || !ops || !ops->create || !ops->next || !ops->destroy || !rows || !n_out || !blocks_hash)
+    return SF_EINVAL;
+  RowBuf rb;
+  // (rows that end while the file is written are not one version's rows: SF_EAGAIN)
+  const int rc = stamped(fd, expect, [&](const sf_file_stamp& before, mode_t mode) {
+    if (!S_ISREG(mode)) return SF_EINVAL;
+    return fd_cut_windows(fd, before, ops, threads, rb, blocks_hash);
+  });
+  if (rc != SF_OK) return rc;
+  if (!rb.grow(1)) return SF_ENOMEM;  // no rows: still a pointer that free() takes
+  *n_out = rb.n;
+  *rows = rb.release();
   return SF_OK;
 }
 

@@ -16,7 +16,6 @@
 // and its last window read is SF_EAGAIN for that file alone: its rows are not
 // valid, every other file's are.  HIP runtime API only: built with the host
 // compiler.
-#include <errno.h>
 #include <fcntl.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -26,13 +25,12 @@
 
 #include <algorithm>
 #include <atomic>
-#include <chrono>
 #include <memory>
-#include <thread>
 #include <vector>
 
 #include "host_sha1.h"
 #include "sf_internal.hpp"
+#include "sf_stage.hpp"
 
 using namespace sfi;
 
@@ -52,36 +50,6 @@ struct Stage {
   std::vector<Piece> pieces;
   uint64_t bytes = 0, blocks = 0;
 };
-
-// Blocks per stage at most: a stage's list and digests stay ~135 MiB.
-constexpr uint64_t kMaxStageBlocks = 1ull << 22;
-
-// SF_TRACE=1: phase times of each call on stderr (probe only).
-struct Trace {
-  bool on;
-  std::chrono::steady_clock::time_point t0, last;
-  double check_ms = 0, read_ms = 0, issue_ms = 0, wait_ms = 0, harvest_ms = 0;
-  Trace() : on(knob(K_TRACE) != 0) { t0 = last = std::chrono::steady_clock::now(); }
-  void lap(double& acc) {
-    if (!on) return;
-    const auto now = std::chrono::steady_clock::now();
-    acc += std::chrono::duration<double, std::milli>(now - last).count();
-    last = now;
-  }
-  void report(uint32_t files, uint64_t blocks, size_t stages) {
-    if (!on) return;
-    const double tot = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    fprintf(stderr,
-            "sf_index_fds_blocks trace: %u files, %llu blocks, %zu stages: check %.2f read %.2f issue %.2f "
-            "wait %.2f harvest %.2f total %.2f ms\n",
-            files, (unsigned long long)blocks, stages, check_ms, read_ms, issue_ms, wait_ms, harvest_ms, tot);
-  }
-};
-
-inline unsigned pool_threads(uint64_t items) {
-  const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
-  return (unsigned)std::min<uint64_t>(std::min(io_threads(), hw), std::max<uint64_t>(1, items));
-}
 
 }  // namespace
 
@@ -103,7 +71,7 @@ static int sf_index_fds_blocks_body(const int* fds, const sf_file_stamp* stamps,
   if (total > cap) return SF_ENOSPC;
   if (total && !out) return SF_EINVAL;
   if (n_files == 0) return SF_OK;
-  Trace tr;
+  Trace tr(knob(K_TRACE) != 0);
 
   // 1. Each file's stamp (against the caller's, taken before its chunker
   // read the file) and its list (against the size in that stamp), on the
@@ -124,17 +92,13 @@ static int sf_index_fds_blocks_body(const int* fds, const sf_file_stamp* stamps,
           else if (!stamp_of(fds[f], &before[f], &mode)) rc = SF_EIO;
           else if (!S_ISREG(mode)) rc = SF_EINVAL;  // a pipe cannot be read twice: sf_index_buffer_blocks
           else if (stamps && !same_stamp(before[f], stamps[f])) rc = SF_EAGAIN;
-          const uint64_t len = before[f].size;
-          for (uint64_t i = 0; rc == SF_OK && i < n_blocks[f]; i++) {
-            if (offsets[f][i] > len || sizes[f][i] > len - offsets[f][i]) rc = SF_ERANGE;
-            else if (i && offsets[f][i] < offsets[f][i - 1]) rc = SF_EINVAL;
-          }
+          if (rc == SF_OK) rc = check_list(before[f].size, offsets[f], sizes[f], n_blocks[f]);
           status[f].store(rc, std::memory_order_relaxed);
         }
       }
     });
   }
-  tr.lap(tr.check_ms);
+  tr.lap(tr.pre_ms[0]);
 
   // 2. Stages: every good file's blocks in windows of at most a stage
   // (consecutive blocks; a larger block is a window of its own), windows
@@ -149,14 +113,9 @@ static int sf_index_fds_blocks_body(const int* fds, const sf_file_stamp* stamps,
     const size_t s0 = stages.size();
     uint64_t npieces = 0;
     for (uint64_t i = 0; i < n_blocks[f]; npieces++) {
-      Piece p{f, i, i + 1, off[i], off[i] + sz[i], 0, i == 0, false, -1};
-      for (i++; i < n_blocks[f] && i - p.b0 < kMaxStageBlocks; i++) {
-        const uint64_t e = std::max(p.w1, off[i] + sz[i]);
-        if (e - p.w0 > target) break;
-        p.w1 = e;
-      }
-      p.b1 = i;
-      p.last = i == n_blocks[f];
+      const ListWindow w = next_list_window(off, sz, n_blocks[f], i, target);
+      i = w.b1;
+      Piece p{f, w.b0, w.b1, w.w0, w.w1, 0, w.b0 == 0, i == n_blocks[f], -1};
       Stage* st = &stages.back();
       const uint64_t nb = p.b1 - p.b0, win = p.w1 - p.w0;
       p.dst = ((st->bytes + 15) & ~15ull) + (p.w0 & 15);
@@ -189,28 +148,21 @@ static int sf_index_fds_blocks_body(const int* fds, const sf_file_stamp* stamps,
     HostLease res;
     hipStream_t* st;
     hipEvent_t* done;
-    void *ddata[2], *pin[2], *dlist[2], *plist[2], *ddig[2], *pdig[2];
-    const uint64_t list_bytes = max_blocks * (sizeof(uint64_t) + sizeof(uint32_t));
+    StageBufs sb[2];
     rc = res.streams(st, done);
-    for (int i = 0; i < 2 && rc == SF_OK; i++) {
-      rc = res.dev(i, max_bytes, &ddata[i]);
-      if (rc == SF_OK) rc = res.pin(i, max_bytes, &pin[i]);
-      if (rc == SF_OK) rc = res.dev(3 + i, max_blocks * 20, &ddig[i]);
-      if (rc == SF_OK) rc = res.pin(3 + i, max_blocks * 20, &pdig[i]);
-      if (rc == SF_OK) rc = res.dev(5 + i, list_bytes, &dlist[i]);
-      if (rc == SF_OK) rc = res.pin(5 + i, list_bytes, &plist[i]);
-    }
+    for (int i = 0; i < 2 && rc == SF_OK; i++)
+      rc = stage_bufs(res, i, max_bytes, max_blocks, max_blocks * kListEntry, &sb[i]);
     if (rc != SF_OK) return rc;
 
     // Rows and blocks_hash of the stage on buffer set b: the pieces on the
     // reader threads (rows; one-piece files' blocks_hash in one SHA-1), then
     // the multi-piece files' streams folded in piece order.
-    int64_t stage_of[2] = {-1, -1};
-    auto harvest = [&](int b) {
+    auto harvest = [&](uint64_t k, int b) {
+      tr.lap(tr.issue_ms);
       if (hipEventSynchronize(done[b]) != hipSuccess) return SF_ENODEV;
-      const Stage& s = stages[(size_t)stage_of[b]];
-      stage_of[b] = -1;
-      const uint8_t* dg = static_cast<const uint8_t*>(pdig[b]);
+      tr.lap(tr.wait_ms);
+      const Stage& s = stages[k];
+      const uint8_t* dg = static_cast<const uint8_t*>(sb[b].pdig);
       std::vector<uint64_t> row0(s.pieces.size());
       for (size_t j = 0, r = 0; j < s.pieces.size(); j++) {
         row0[j] = r;
@@ -244,18 +196,11 @@ static int sf_index_fds_blocks_body(const int* fds, const sf_file_stamp* stamps,
         sf_host_sha1_update(&h, dg + 20 * row0[j], (p.b1 - p.b0) * 20);
         if (p.last) sf_host_sha1_final(&h, blocks_hashes + 20ull * p.f);
       }
+      tr.lap(tr.harvest_ms);
       return SF_OK;
     };
 
-    for (size_t k = 0; k < stages.size() && rc == SF_OK; k++) {
-      const int b = (int)(k & 1);
-      if (stage_of[b] >= 0) {  // stage k-2 (stage k-1 is later in file order)
-        tr.lap(tr.issue_ms);
-        if (hipEventSynchronize(done[b]) != hipSuccess) { rc = SF_ENODEV; break; }
-        tr.lap(tr.wait_ms);
-        if ((rc = harvest(b)) != SF_OK) break;
-        tr.lap(tr.harvest_ms);
-      }
+    auto issue = [&](uint64_t k, int b) {
       const Stage& s = stages[k];
       // read: (piece, <= 16 MiB slice) work items; a short read marks the
       // piece's file SF_EIO, the stage goes on
@@ -266,21 +211,16 @@ static int sf_index_fds_blocks_body(const int* fds, const sf_file_stamp* stamps,
         const uint64_t win = s.pieces[j].w1 - s.pieces[j].w0;
         for (uint64_t a = 0; a < win; a += kSlice) items.push_back({j, a, std::min(win, a + kSlice)});
       }
-      uint8_t* dst = static_cast<uint8_t*>(pin[b]);
+      uint8_t* dst = static_cast<uint8_t*>(sb[b].pin);
       std::atomic<size_t> next{0};
       run_pool(pool_threads(items.size()), [&] {
         for (size_t i; (i = next.fetch_add(1)) < items.size();) {
           const Item& it = items[i];
           const Piece& p = s.pieces[it.j];
-          for (uint64_t got = it.a; got < it.e;) {
-            const ssize_t r = pread(fds[p.f], dst + p.dst + got, it.e - got, (off_t)(p.w0 + got));
-            if (r < 0 && errno == EINTR) continue;  // a signal (profiler, Python handler) is not a bad file
-            if (r <= 0) {  // error, or EOF before the size in the stamp: the file shrank
-              int ok = SF_OK;
-              status[p.f].compare_exchange_strong(ok, SF_EIO);
-              break;
-            }
-            got += (uint64_t)r;
+          // an error, or EOF before the size in the stamp (the file shrank)
+          if (!read_fully(fds[p.f], dst + p.dst + it.a, p.w0 + it.a, it.e - it.a)) {
+            int ok = SF_OK;
+            status[p.f].compare_exchange_strong(ok, SF_EIO);
           }
         }
       });
@@ -298,7 +238,7 @@ static int sf_index_fds_blocks_body(const int* fds, const sf_file_stamp* stamps,
       }
       tr.lap(tr.read_ms);
       // the stage's list: offsets in the stage buffer, sizes
-      uint64_t* lo = static_cast<uint64_t*>(plist[b]);
+      uint64_t* lo = static_cast<uint64_t*>(sb[b].paux);
       uint32_t* lz = reinterpret_cast<uint32_t*>(lo + s.blocks);
       uint64_t r = 0;
       for (const Piece& p : s.pieces) {
@@ -309,33 +249,21 @@ static int sf_index_fds_blocks_body(const int* fds, const sf_file_stamp* stamps,
           lz[r] = sz[i];
         }
       }
-      const uint64_t* d_off = static_cast<const uint64_t*>(dlist[b]);
+      const uint64_t* d_off = static_cast<const uint64_t*>(sb[b].daux);
       const uint32_t* d_sz = reinterpret_cast<const uint32_t*>(d_off + s.blocks);
-      if ((s.bytes && hipMemcpyAsync(ddata[b], pin[b], s.bytes, hipMemcpyHostToDevice, st[b]) != hipSuccess) ||
-          hipMemcpyAsync(dlist[b], plist[b], s.blocks * (sizeof(uint64_t) + sizeof(uint32_t)), hipMemcpyHostToDevice,
-                         st[b]) != hipSuccess) {
-        rc = SF_ENODEV;
-        break;
-      }
+      if ((s.bytes && hipMemcpyAsync(sb[b].ddata, sb[b].pin, s.bytes, hipMemcpyHostToDevice, st[b]) != hipSuccess) ||
+          hipMemcpyAsync(sb[b].daux, sb[b].paux, s.blocks * kListEntry, hipMemcpyHostToDevice, st[b]) != hipSuccess)
+        return SF_ENODEV;
       // every block was checked to lie in its file, so in its window: no status word
-      if ((rc = launch_table(ddata[b], s.bytes, d_off, d_sz, s.blocks, ddig[b], nullptr, st[b])) != SF_OK) break;
-      if (hipMemcpyAsync(pdig[b], ddig[b], s.blocks * 20, hipMemcpyDeviceToHost, st[b]) != hipSuccess ||
-          hipEventRecord(done[b], st[b]) != hipSuccess) {
-        rc = SF_ENODEV;
-        break;
-      }
-      stage_of[b] = (int64_t)k;
-    }
-    tr.lap(tr.issue_ms);
-    // the (at most two) stages still in flight, in file order
-    int order[2] = {0, 1};
-    if (stage_of[0] >= 0 && stage_of[1] >= 0 && stage_of[1] < stage_of[0]) std::swap(order[0], order[1]);
-    for (int b : order)
-      if (stage_of[b] >= 0) {
-        const int r2 = harvest(b);
-        if (rc == SF_OK) rc = r2;
-      }
-    tr.lap(tr.harvest_ms);
+      if (const int rl = launch_table(sb[b].ddata, s.bytes, d_off, d_sz, s.blocks, sb[b].ddig, nullptr, st[b]))
+        return rl;
+      if (hipMemcpyAsync(sb[b].pdig, sb[b].ddig, s.blocks * 20, hipMemcpyDeviceToHost, st[b]) != hipSuccess ||
+          hipEventRecord(done[b], st[b]) != hipSuccess)
+        return SF_ENODEV;
+      tr.lap(tr.issue_ms);
+      return SF_OK;
+    };
+    rc = two_stage(stages.size(), issue, harvest);
   }
   if (rc != SF_OK) return rc;  // a device error: no file's rows are valid
 
@@ -353,7 +281,12 @@ static int sf_index_fds_blocks_body(const int* fds, const sf_file_stamp* stamps,
       sf_host_sha1_impl(reinterpret_cast<const uint8_t*>(""), 0, blocks_hashes + 20ull * f, 0);
     }
   }
-  tr.report(n_files, total, stages.size());
+  if (tr.on) {
+    char head[160];
+    snprintf(head, sizeof(head), "sf_index_fds_blocks trace: %u files, %llu blocks, %zu stages: check %.2f", n_files,
+             (unsigned long long)total, stages.size(), tr.pre_ms[0]);
+    tr.report(head);
+  }
   if (first_bad >= 0) {
     if (bad_file) *bad_file = (uint32_t)first_bad;
     return status[first_bad].load();

@@ -1,7 +1,6 @@
 // sf_files.cpp -- sf_index_files (include/syncfast_amd.h): many files from
 // disk through one pipeline, what index_path (src/index.rs:685-715) does with
 // one index_file per file.  HIP runtime API only: built with the host compiler.
-#include <errno.h>
 #include <fcntl.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -13,41 +12,15 @@
 
 #include <algorithm>
 #include <atomic>
-#include <chrono>
-#include <thread>
 #include <vector>
 
 #include "host_sha1.h"
 #include "sf_internal.hpp"
+#include "sf_stage.hpp"
 
 using namespace sfi;
 
 namespace {
-
-// SF_TRACE=1: phase times of each sf_index_files call on stderr (probe only).
-struct Trace {
-  bool on;
-  std::chrono::steady_clock::time_point t0, last;
-  double stat_ms = 0, big_ms = 0, wait_ms = 0, harvest_ms = 0, read_ms = 0, issue_ms = 0;
-  Trace() {
-    on = knob(K_TRACE) != 0;
-    t0 = last = std::chrono::steady_clock::now();
-  }
-  void lap(double& acc) {
-    if (!on) return;
-    const auto now = std::chrono::steady_clock::now();
-    acc += std::chrono::duration<double, std::milli>(now - last).count();
-    last = now;
-  }
-  void report(uint32_t files, size_t stages) {
-    if (!on) return;
-    const double tot = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    fprintf(stderr,
-            "sf_index_files trace: %u files, %zu stages: stat %.2f big %.2f read %.2f issue %.2f wait %.2f "
-            "harvest %.2f total %.2f ms\n",
-            files, stages, stat_ms, big_ms, read_ms, issue_ms, wait_ms, harvest_ms, tot);
-  }
-};
 
 struct FileStage {
   std::vector<uint32_t> files;    // file indices, in order
@@ -78,12 +51,7 @@ int read_stage(const char* const* paths, const FileStage& st, const std::vector<
       const int fd = open(paths[f], O_RDONLY);
       bool ok = fd >= 0;
       uint8_t* d = dst + st.desc[it.k].offset;
-      for (uint64_t got = it.a; ok && got < it.b;) {
-        const ssize_t r = pread(fd, d + got, it.b - got, (off_t)got);
-        if (r < 0 && errno == EINTR) continue;  // a signal (profiler, Python handler) is not a bad file
-        if (r <= 0) ok = false;  // error, or EOF before the size stat() gave
-        else got += (uint64_t)r;
-      }
+      ok = ok && read_fully(fd, d + it.a, it.a, it.b - it.a);  // an error, or EOF before the size stat() gave
       if (fd >= 0) close(fd);
       if (!ok) {
         int64_t want = -1;
@@ -92,9 +60,7 @@ int read_stage(const char* const* paths, const FileStage& st, const std::vector<
       }
     }
   };
-  const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
-  const unsigned nthreads = (unsigned)std::min<size_t>(std::min(io_threads(), hw), std::max<size_t>(1, items.size()));
-  run_pool(nthreads, worker);
+  run_pool(pool_threads(items.size()), worker);
   return rc.load();
 }
 
@@ -109,7 +75,7 @@ static int sf_index_files_body(const char* const* paths, uint32_t n_files, uint3
   if (rc) return rc;
   if (n_files && (!paths || !first_row || !blocks_hashes)) return SF_EINVAL;
   const uint32_t bs = block_size;
-  Trace tr;
+  Trace tr(knob(K_TRACE) != 0);
   auto fail = [&](uint32_t f, int code) {
     if (bad_file) *bad_file = f;
     return code;
@@ -136,11 +102,9 @@ static int sf_index_files_body(const char* const* paths, uint32_t n_files, uint3
         }
       }
     };
-    const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
-    const unsigned nthreads = (unsigned)std::min<uint64_t>(std::min(io_threads(), hw), nchunks);
-    run_pool(nthreads, worker);
+    run_pool(pool_threads(nchunks), worker);
   }
-  tr.lap(tr.stat_ms);
+  tr.lap(tr.pre_ms[0]);
   uint64_t total = 0;
   for (uint32_t f = 0; f < n_files; f++) {
     if (st_rc[f] != SF_OK) return fail(f, st_rc[f]);
@@ -178,7 +142,7 @@ static int sf_index_files_body(const char* const* paths, uint32_t n_files, uint3
     if (rc == SF_ENOSPC || (rc == SF_OK && got != want)) return fail(f, SF_EIO);  // changed meanwhile
     if (rc) return rc == SF_EIO ? fail(f, rc) : rc;
   }
-  tr.lap(tr.big_ms);
+  tr.lap(tr.pre_ms[1]);
   if (stages.empty()) return SF_OK;
 
   // 3. Pipeline: read stage k (host threads) while stage k-1 copies and
@@ -194,17 +158,8 @@ static int sf_index_files_body(const char* const* paths, uint32_t n_files, uint3
   hipStream_t* streams;
   hipEvent_t* done;
   rc = res.streams(streams, done);
-  struct Buf {
-    void* p;
-  } ddata[2], ddig[2], dfh[2], pin[2], pdig[2], pfh[2];
-  for (int i = 0; i < 2 && rc == SF_OK; i++) {
-    rc = res.dev(i, max_bytes, &ddata[i].p);
-    if (rc == SF_OK) rc = res.dev(3 + i, max_rows * 20, &ddig[i].p);
-    if (rc == SF_OK) rc = res.dev(5 + i, max_files * 20, &dfh[i].p);
-    if (rc == SF_OK) rc = res.pin(i, std::min<uint64_t>(max_bytes, stage), &pin[i].p);
-    if (rc == SF_OK) rc = res.pin(3 + i, max_rows * 20, &pdig[i].p);
-    if (rc == SF_OK) rc = res.pin(5 + i, max_files * 20, &pfh[i].p);
-  }
+  StageBufs sb[2];  // aux: the stage's files' blocks_hash values
+  for (int i = 0; i < 2 && rc == SF_OK; i++) rc = stage_bufs(res, i, max_bytes, max_rows, max_files * 20, &sb[i]);
   if (rc != SF_OK) return rc;
   // Per stage: each file's blocks_hash from a device chain (one lane per
   // file, after the stage's blocks) while the runs are short; on the host
@@ -222,11 +177,12 @@ static int sf_index_files_body(const char* const* paths, uint32_t n_files, uint3
   for (size_t k = 0; k < stages.size(); k++)
     for (uint32_t f : stages[k].files)
       if ((first_row[f + 1] - first_row[f]) * 20 > kDevChainMaxRun) dev_bh[k] = 0;
-  auto harvest = [&](size_t k) {
+  auto harvest = [&](uint64_t k, int b) {
+    if (hipEventSynchronize(done[b]) != hipSuccess) return SF_ENODEV;
+    tr.lap(tr.wait_ms);
     const FileStage& st = stages[k];
-    const int b = (int)(k & 1);
-    const uint8_t* dg = static_cast<const uint8_t*>(pdig[b].p);
-    const uint8_t* fh = static_cast<const uint8_t*>(pfh[b].p);
+    const uint8_t* dg = static_cast<const uint8_t*>(sb[b].pdig);
+    const uint8_t* fh = static_cast<const uint8_t*>(sb[b].paux);
     uint64_t r = 0;
     for (size_t j = 0; j < st.files.size(); j++) {
       const uint32_t f = st.files[j];
@@ -240,48 +196,41 @@ static int sf_index_files_body(const char* const* paths, uint32_t n_files, uint3
       if (dev_bh[k]) memcpy(blocks_hashes + 20ull * f, fh + 20 * j, 20);
       else sf_host_sha1_impl(dg + 20 * (r - nb), nb * 20, blocks_hashes + 20ull * f, 0);
     }
+    tr.lap(tr.harvest_ms);
     return SF_OK;
   };
   std::atomic<int64_t> bad{-1};
-  for (size_t k = 0; k < stages.size() && rc == SF_OK; k++) {
-    const int b = (int)(k & 1);
+  auto issue = [&](uint64_t k, int b) {
     const FileStage& st = stages[k];
-    tr.lap(tr.issue_ms);
-    if (k >= 2) {
-      if (hipEventSynchronize(done[b]) != hipSuccess) { rc = SF_ENODEV; break; }
-      tr.lap(tr.wait_ms);
-      if ((rc = harvest(k - 2)) != SF_OK) break;
-      tr.lap(tr.harvest_ms);
-    }
-    rc = read_stage(paths, st, size, static_cast<uint8_t*>(pin[b].p), bad);
+    int r = read_stage(paths, st, size, static_cast<uint8_t*>(sb[b].pin), bad);
     tr.lap(tr.read_ms);
-    if (rc) break;
+    if (r) return r;
     hipStream_t s = streams[b];
     // H2D: the whole stage in one copy
-    if (st.bytes && hipMemcpyAsync(ddata[b].p, pin[b].p, st.bytes, hipMemcpyHostToDevice, s) != hipSuccess) {
-      rc = SF_ENODEV;
-      break;
-    }
+    if (st.bytes && hipMemcpyAsync(sb[b].ddata, sb[b].pin, st.bytes, hipMemcpyHostToDevice, s) != hipSuccess)
+      return SF_ENODEV;
     uint64_t nb = 0;
-    rc = sf_index_device_batch(ddata[b].p, st.bytes, st.desc.data(), (uint32_t)st.files.size(), bs, ddig[b].p,
-                               max_rows, dev_bh[k] ? dfh[b].p : nullptr, nullptr, &nb, nullptr, s);
-    if (rc) break;
-    if ((nb && hipMemcpyAsync(pdig[b].p, ddig[b].p, nb * 20, hipMemcpyDeviceToHost, s) != hipSuccess) ||
-        (dev_bh[k] && hipMemcpyAsync(pfh[b].p, dfh[b].p, st.files.size() * 20, hipMemcpyDeviceToHost, s) != hipSuccess) ||
-        hipEventRecord(done[b], s) != hipSuccess) {
-      rc = SF_ENODEV;
-      break;
-    }
-  }
-  tr.lap(tr.issue_ms);
+    r = sf_index_device_batch(sb[b].ddata, st.bytes, st.desc.data(), (uint32_t)st.files.size(), bs, sb[b].ddig,
+                              max_rows, dev_bh[k] ? sb[b].daux : nullptr, nullptr, &nb, nullptr, s);
+    if (r) return r;
+    if ((nb && hipMemcpyAsync(sb[b].pdig, sb[b].ddig, nb * 20, hipMemcpyDeviceToHost, s) != hipSuccess) ||
+        (dev_bh[k] &&
+         hipMemcpyAsync(sb[b].paux, sb[b].daux, st.files.size() * 20, hipMemcpyDeviceToHost, s) != hipSuccess) ||
+        hipEventRecord(done[b], s) != hipSuccess)
+      return SF_ENODEV;
+    tr.lap(tr.issue_ms);
+    return SF_OK;
+  };
+  rc = two_stage(stages.size(), issue, harvest);
   for (int i = 0; i < 2; i++)
     if (hipStreamSynchronize(streams[i]) != hipSuccess && rc == SF_OK) rc = SF_ENODEV;
   tr.lap(tr.wait_ms);
-  if (rc == SF_OK)
-    for (size_t k = stages.size() >= 2 ? stages.size() - 2 : 0; k < stages.size() && rc == SF_OK; k++)
-      rc = harvest(k);
-  tr.lap(tr.harvest_ms);
-  tr.report(n_files, stages.size());
+  if (tr.on) {
+    char head[160];
+    snprintf(head, sizeof(head), "sf_index_files trace: %u files, %zu stages: stat %.2f big %.2f", n_files,
+             stages.size(), tr.pre_ms[0], tr.pre_ms[1]);
+    tr.report(head);
+  }
   if (rc == SF_EIO && bad.load() >= 0) return fail((uint32_t)bad.load(), rc);
   return rc;
 }

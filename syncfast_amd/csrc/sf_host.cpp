@@ -20,11 +20,11 @@
 #include <atomic>
 #include <functional>
 #include <mutex>
-#include <thread>
 #include <vector>
 
 #include "host_sha1.h"
 #include "sf_internal.hpp"
+#include "sf_stage.hpp"
 
 namespace sfi __attribute__((visibility("hidden"))) {
 std::mutex g_res_mu[kMaxDevices];
@@ -262,9 +262,9 @@ int index_inplace(const uint8_t* data, uint64_t len, uint32_t bs, sf_block_sig* 
   hipEvent_t* done;
   void *ddata[2], *ddig, *pdig;
   int rc = res.streams(st, done);
-  for (int i = 0; i < 2 && rc == SF_OK; i++) rc = res.dev(i, stage, &ddata[i]);
-  if (rc == SF_OK) rc = res.dev(2, nblocks * 20, &ddig);
-  if (rc == SF_OK) rc = res.pin(2, nblocks * 20, &pdig);
+  for (int i = 0; i < 2 && rc == SF_OK; i++) rc = res.dev(kSlotData + i, stage, &ddata[i]);
+  if (rc == SF_OK) rc = res.dev(kSlotFileTable, nblocks * 20, &ddig);
+  if (rc == SF_OK) rc = res.pin(kSlotFileTable, nblocks * 20, &pdig);
   if (rc != SF_OK) return rc;
   sf_host_sha1_stream bh;
   sf_host_sha1_begin(&bh);
@@ -331,6 +331,34 @@ int index_inplace(const uint8_t* data, uint64_t len, uint32_t bs, sf_block_sig* 
   return SF_OK;
 }
 
+// The host end of the two wire streams: chunk buffer b's bytes come back into
+// its pinned buffer (copy_back, after the kernels that built them), and are
+// written to fd, in order, once they are there (flush).
+struct WireOut {
+  int fd;
+  hipEvent_t* ev;
+  StageBufs* sb;
+  uint64_t bytes_of[2] = {0, 0}, written = 0;
+  int copy_back(int b, hipStream_t s) {
+    if (hipMemcpyAsync(sb[b].pin, sb[b].ddata, bytes_of[b], hipMemcpyDeviceToHost, s) != hipSuccess ||
+        hipEventRecord(ev[b], s) != hipSuccess)
+      return SF_ENODEV;
+    return SF_OK;
+  }
+  int flush(int b) {
+    if (hipEventSynchronize(ev[b]) != hipSuccess) return SF_ENODEV;
+    const uint8_t* p = static_cast<const uint8_t*>(sb[b].pin);
+    for (uint64_t done = 0; done < bytes_of[b];) {
+      const ssize_t w = write(fd, p + done, bytes_of[b] - done);
+      if (w < 0 && errno == EINTR) continue;
+      if (w <= 0) return SF_EIO;
+      done += (uint64_t)w;
+      written += (uint64_t)w;
+    }
+    return SF_OK;
+  }
+};
+
 }  // namespace
 
 extern "C" {
@@ -376,51 +404,35 @@ static int sf_wire_file_blocks_fd_body(const void* d_digests, uint64_t n_blocks,
   HostLease res;
   hipStream_t* st;
   hipEvent_t* ev;
-  void *dout[2], *pin[2];
+  StageBufs sb[2];
   hipEvent_t ready = nullptr;
-  uint64_t bytes_of[2] = {0, 0};
   int rc = res.streams(st, ev);
-  for (int i = 0; i < 2 && rc == SF_OK; i++) {
-    rc = res.dev(i, cap, &dout[i]);
-    if (rc == SF_OK) rc = res.pin(i, cap, &pin[i]);
-  }
+  for (int i = 0; i < 2 && rc == SF_OK; i++) rc = stage_bufs(res, i, cap, kNoBuf, kNoBuf, &sb[i]);
   if (rc != SF_OK) return rc;
   SF_HIP(hipEventCreateWithFlags(&ready, hipEventDisableTiming));
   if (hipEventRecord(ready, as_stream(stream)) != hipSuccess ||  // the digests are produced on the caller's stream
       hipStreamWaitEvent(st[0], ready, 0) != hipSuccess || hipStreamWaitEvent(st[1], ready, 0) != hipSuccess)
     rc = SF_ENODEV;
-  uint64_t written = 0;
-  auto flush = [&](int b) {  // write chunk buffer b to fd, in order
-    if (hipEventSynchronize(ev[b]) != hipSuccess) return SF_ENODEV;
-    const uint8_t* p = static_cast<const uint8_t*>(pin[b]);
-    for (uint64_t done = 0; done < bytes_of[b];) {
-      const ssize_t w = write(fd, p + done, bytes_of[b] - done);
-      if (w < 0 && errno == EINTR) continue;
-      if (w <= 0) return SF_EIO;
-      done += (uint64_t)w;
-      written += (uint64_t)w;
-    }
-    return SF_OK;
-  };
-  // chunk k: device builds its messages, D2H into pin[k&1]; the host writes
-  // chunk k-2 while the device works on chunk k.
-  for (uint64_t k = 0; k < nchunks && rc == SF_OK; k++) {
-    const int b = (int)(k & 1);
-    if (k >= 2 && (rc = flush(b)) != SF_OK) break;
-    const uint64_t i0 = k * per, n = std::min(per, nb - i0);
-    const bool final_chunk = i0 + n == nb;
-    const uint32_t lsz = final_chunk ? last : block_size;
-    bytes_of[b] = (n - 1) * msg + (final_chunk ? 33 + dl : msg);
-    if (launch_wire(static_cast<const uint8_t*>(d_digests) + i0 * 20, n, block_size, lsz,
-                    static_cast<uint8_t*>(dout[b]), st[b]) != SF_OK ||
-        hipMemcpyAsync(pin[b], dout[b], bytes_of[b], hipMemcpyDeviceToHost, st[b]) != hipSuccess ||
-        hipEventRecord(ev[b], st[b]) != hipSuccess)
-      rc = SF_ENODEV;
-  }
-  for (uint64_t k = nchunks >= 2 ? nchunks - 2 : 0; k < nchunks && rc == SF_OK; k++) rc = flush((int)(k & 1));
+  WireOut w{fd, ev, sb};
+  // chunk k: device builds its messages, D2H into its pinned buffer; the host
+  // writes chunk k-2 while the device works on chunk k.
+  if (rc == SF_OK)
+    rc = two_stage(
+        nchunks,
+        [&](uint64_t k, int b) {
+          const uint64_t i0 = k * per, n = std::min(per, nb - i0);
+          const bool final_chunk = i0 + n == nb;
+          const uint32_t lsz = final_chunk ? last : block_size;
+          w.bytes_of[b] = (n - 1) * msg + (final_chunk ? 33 + dl : msg);
+          if (launch_wire(static_cast<const uint8_t*>(d_digests) + i0 * 20, n, block_size, lsz,
+                          static_cast<uint8_t*>(sb[b].ddata), st[b]) != SF_OK)
+            return SF_ENODEV;
+          return w.copy_back(b, st[b]);
+        },
+        [&](uint64_t, int b) { return w.flush(b); });
   for (int i = 0; i < 2; i++) (void)hipStreamSynchronize(st[i]);
   (void)hipEventDestroy(ready);
-  if (n_written) *n_written = written;
+  if (n_written) *n_written = w.written;
   return rc;
 }
 
@@ -460,42 +472,23 @@ static int sf_wire_blocks_fd_body(const void* d_digests, const uint32_t* d_sizes
   HostLease res;
   hipStream_t* st;
   hipEvent_t* ev;
-  void *dout[2], *pin[2];
-  uint64_t bytes_of[2] = {0, 0};
+  StageBufs sb[2];
   rc = res.streams(st, ev);
-  for (int i = 0; i < 2 && rc == SF_OK; i++) {
-    rc = res.dev(i, cap, &dout[i]);
-    if (rc == SF_OK) rc = res.pin(i, cap, &pin[i]);
-  }
+  for (int i = 0; i < 2 && rc == SF_OK; i++) rc = stage_bufs(res, i, cap, kNoBuf, kNoBuf, &sb[i]);
   if (rc != SF_OK) return rc;  // (the plan is complete: cs was synchronised above)
-  uint64_t written = 0;
-  auto flush = [&](int b) {
-    if (hipEventSynchronize(ev[b]) != hipSuccess) return SF_ENODEV;
-    const uint8_t* p = static_cast<const uint8_t*>(pin[b]);
-    for (uint64_t done = 0; done < bytes_of[b];) {
-      const ssize_t w = write(fd, p + done, bytes_of[b] - done);
-      if (w < 0 && errno == EINTR) continue;
-      if (w <= 0) return SF_EIO;
-      done += (uint64_t)w;
-      written += (uint64_t)w;
-    }
-    return SF_OK;
-  };
-  for (uint64_t k = 0; k < nchunks && rc == SF_OK; k++) {
-    const int b = (int)(k & 1);
-    if (k >= 2 && (rc = flush(b)) != SF_OK) break;
-    const uint64_t i0 = k * per, cnt = std::min(per, n_blocks - i0), base = k ? cend[k - 1] : 0;
-    bytes_of[b] = cend[k] - base;
-    if ((rc = wire_build(static_cast<const uint8_t*>(d_digests), d_sizes, ends, i0, cnt, base,
-                         static_cast<uint8_t*>(dout[b]), st[b])) != SF_OK)
-      break;
-    if (hipMemcpyAsync(pin[b], dout[b], bytes_of[b], hipMemcpyDeviceToHost, st[b]) != hipSuccess ||
-        hipEventRecord(ev[b], st[b]) != hipSuccess)
-      rc = SF_ENODEV;
-  }
-  for (uint64_t k = nchunks >= 2 ? nchunks - 2 : 0; k < nchunks && rc == SF_OK; k++) rc = flush((int)(k & 1));
+  WireOut w{fd, ev, sb};
+  rc = two_stage(
+      nchunks,
+      [&](uint64_t k, int b) {
+        const uint64_t i0 = k * per, cnt = std::min(per, n_blocks - i0), base = k ? cend[k - 1] : 0;
+        w.bytes_of[b] = cend[k] - base;
+        const int r = wire_build(static_cast<const uint8_t*>(d_digests), d_sizes, ends, i0, cnt, base,
+                                 static_cast<uint8_t*>(sb[b].ddata), st[b]);
+        return r != SF_OK ? r : w.copy_back(b, st[b]);
+      },
+      [&](uint64_t, int b) { return w.flush(b); });
   for (int i = 0; i < 2; i++) (void)hipStreamSynchronize(st[i]);  // before the plan is freed on cs
-  if (n_written) *n_written = written;
+  if (n_written) *n_written = w.written;
   return rc;
 }
 
@@ -520,85 +513,50 @@ inline uint64_t file_stage_bytes(uint32_t bs) {
 
 template <typename FillFn, typename EmitFn>
 int staged_pipeline(uint32_t bs, uint64_t stage, FillFn fill, EmitFn emit, uint8_t* blocks_hash) {
-  const uint64_t sblocks = stage / bs;
   HostLease res;
   hipStream_t* st;
   hipEvent_t* done;
-  void *ddata[2], *pin[2], *ddig[2], *pdig[2];
+  StageBufs sb[2];
   int rc = res.streams(st, done);
-  for (int i = 0; i < 2 && rc == SF_OK; i++) {
-    rc = res.dev(i, stage, &ddata[i]);
-    if (rc == SF_OK) rc = res.pin(i, stage, &pin[i]);
-    if (rc == SF_OK) rc = res.dev(3 + i, sblocks * 20, &ddig[i]);
-    if (rc == SF_OK) rc = res.pin(3 + i, sblocks * 20, &pdig[i]);
-  }
+  for (int i = 0; i < 2 && rc == SF_OK; i++) rc = stage_bufs(res, i, stage, stage / bs, kNoBuf, &sb[i]);
   if (rc != SF_OK) return rc;
   sf_host_sha1_stream bh;
   sf_host_sha1_begin(&bh);
   uint64_t bytes_of[2] = {0, 0}, first_of[2] = {0, 0};
-  bool busy[2] = {false, false};
-  auto harvest = [&](int b) {
-    if (hipEventSynchronize(done[b]) != hipSuccess) return SF_ENODEV;
-    busy[b] = false;
-    const uint64_t nb = ceil_div(bytes_of[b], bs);
-    const uint8_t* dg = static_cast<const uint8_t*>(pdig[b]);
-    const int r = emit(first_of[b], nb, dg, bytes_of[b]);
-    if (r != SF_OK) return r;
-    if (blocks_hash) sf_host_sha1_update(&bh, dg, nb * 20);
-    return SF_OK;
-  };
   uint64_t total = 0;
   bool eof = false;
-  for (uint64_t k = 0; !eof && rc == SF_OK; k++) {
-    const int b = (int)(k & 1);
-    if (busy[b] && (rc = harvest(b)) != SF_OK) break;  // stage k-2 (stage k-1 is later in file order)
-    uint8_t* dst = static_cast<uint8_t*>(pin[b]);
-    uint64_t n = 0;
-    if ((rc = fill(dst, total, stage, &n, &eof)) != SF_OK || n == 0) break;
-    const uint64_t nb = ceil_div(n, bs);
-    bytes_of[b] = n;
-    first_of[b] = total / bs;  // every earlier stage was whole blocks
-    total += n;
-    if (hipMemcpyAsync(ddata[b], dst, n, hipMemcpyHostToDevice, st[b]) != hipSuccess) { rc = SF_ENODEV; break; }
-    if ((rc = launch_fixed(ddata[b], n, bs, nb, ddig[b], st[b])) != SF_OK) break;
-    if (hipMemcpyAsync(pdig[b], ddig[b], nb * 20, hipMemcpyDeviceToHost, st[b]) != hipSuccess ||
-        hipEventRecord(done[b], st[b]) != hipSuccess) { rc = SF_ENODEV; break; }
-    busy[b] = true;
-  }
-  // the (at most two) stages still in flight, in file order
-  int order[2] = {0, 1};
-  if (busy[0] && busy[1] && first_of[1] < first_of[0]) std::swap(order[0], order[1]);
-  for (int b : order)
-    if (busy[b]) {
-      const int r = harvest(b);
-      if (rc == SF_OK) rc = r;
-    }
+  rc = two_stage(
+      UINT64_MAX,
+      [&](uint64_t, int b) {
+        if (eof) return kNoMoreStages;
+        uint8_t* dst = static_cast<uint8_t*>(sb[b].pin);
+        uint64_t n = 0;
+        const int r = fill(dst, total, stage, &n, &eof);
+        if (r != SF_OK) return r;
+        if (n == 0) return kNoMoreStages;
+        const uint64_t nb = ceil_div(n, bs);
+        bytes_of[b] = n;
+        first_of[b] = total / bs;  // every earlier stage was whole blocks
+        total += n;
+        if (hipMemcpyAsync(sb[b].ddata, dst, n, hipMemcpyHostToDevice, st[b]) != hipSuccess) return SF_ENODEV;
+        if (const int rl = launch_fixed(sb[b].ddata, n, bs, nb, sb[b].ddig, st[b])) return rl;
+        if (hipMemcpyAsync(sb[b].pdig, sb[b].ddig, nb * 20, hipMemcpyDeviceToHost, st[b]) != hipSuccess ||
+            hipEventRecord(done[b], st[b]) != hipSuccess)
+          return SF_ENODEV;
+        return SF_OK;
+      },
+      [&](uint64_t, int b) {
+        if (hipEventSynchronize(done[b]) != hipSuccess) return SF_ENODEV;
+        const uint64_t nb = ceil_div(bytes_of[b], bs);
+        const uint8_t* dg = static_cast<const uint8_t*>(sb[b].pdig);
+        const int r = emit(first_of[b], nb, dg, bytes_of[b]);
+        if (r != SF_OK) return r;
+        if (blocks_hash) sf_host_sha1_update(&bh, dg, nb * 20);
+        return SF_OK;
+      });
   if (rc == SF_OK && blocks_hash) sf_host_sha1_final(&bh, blocks_hash);
   return rc;
 }
-
-// Rows in a growing malloc'd buffer (sf_index_fd; the sequential route of
-// sf_index_file).
-struct RowBuf {
-  sf_block_sig* p = nullptr;
-  uint64_t n = 0, cap = 0;
-  ~RowBuf() { free(p); }
-  bool grow(uint64_t need) {
-    if (need <= cap) return true;
-    uint64_t c = std::max<uint64_t>({need, 2 * cap, 1024});
-    void* q = realloc(p, c * sizeof(sf_block_sig));
-    if (!q) return false;
-    p = static_cast<sf_block_sig*>(q);
-    cap = c;
-    return true;
-  }
-  sf_block_sig* release() {
-    sf_block_sig* q = p;
-    p = nullptr;
-    n = cap = 0;
-    return q;
-  }
-};
 
 inline void write_rows(sf_block_sig* o, uint64_t first, uint64_t nb, const uint8_t* dg, uint64_t bytes, uint32_t bs) {
   for (uint64_t i = 0; i < nb; i++) {
@@ -648,7 +606,6 @@ namespace sfi {
 // Bytes [base, base + len) of the file (base a multiple of bs: a shard of
 // one logical file); row offsets are file offsets.
 int index_file_pread(int fd, uint64_t base, uint64_t len, uint32_t bs, sf_block_sig* out, uint8_t* blocks_hash) {
-  const unsigned nthreads = std::max(1u, std::min(io_threads(), std::thread::hardware_concurrency()));
   const bool adv = fadvise_on();
   if (adv) (void)posix_fadvise(fd, (off_t)base, (off_t)len, POSIX_FADV_SEQUENTIAL);
   uint64_t window = 0;
@@ -658,27 +615,9 @@ int index_file_pread(int fd, uint64_t base, uint64_t len, uint32_t bs, sf_block_
     *eof = off + n >= len;
     if (adv && !*eof)
       (void)posix_fadvise(fd, (off_t)(base + off + n), (off_t)std::min(cap, len - off - n), POSIX_FADV_WILLNEED);
-    auto read_slice = [&](uint64_t a, uint64_t b) {
-      for (uint64_t got = a; got < b;) {
-        const ssize_t r = pread(fd, dst + got, b - got, (off_t)(base + off + got));
-        if (r < 0 && errno == EINTR) continue;
-        if (r <= 0) return SF_EIO;
-        got += (uint64_t)r;
-      }
-      return SF_OK;
-    };
-    const uint64_t slice = std::max<uint64_t>(4ull << 20, ceil_div(n, nthreads));
-    const uint64_t nslices = ceil_div(n, slice);
-    std::atomic<uint64_t> next{0};
-    std::atomic<int> rc{SF_OK};
-    run_pool((unsigned)std::min<uint64_t>(nthreads, nslices), [&] {
-      for (uint64_t i; (i = next.fetch_add(1)) < nslices && rc.load() == SF_OK;) {
-        const int r = read_slice(i * slice, std::min(n, (i + 1) * slice));
-        if (r != SF_OK) rc.store(r);
-      }
-    });
+    const int rc = read_sliced(fd, dst, base + off, n);
     read_hook(window++);
-    return rc.load();
+    return rc;
   };
   auto emit = [&](uint64_t first, uint64_t nb, const uint8_t* dg, uint64_t bytes) {
     write_rows(out + first, base / bs + first, nb, dg, bytes, bs);
@@ -694,28 +633,11 @@ namespace {
 // Copy n bytes into a pinned stage with several threads (one thread moves
 // ~10-16 GB/s, below the PCIe link the stage is waiting for).
 inline void par_memcpy(uint8_t* dst, const uint8_t* src, uint64_t n) {
-  const unsigned nthreads = std::max(1u, std::min(io_threads(), std::thread::hardware_concurrency()));
-  const uint64_t slice = std::max<uint64_t>(4ull << 20, ceil_div(n, nthreads));
-  const uint64_t nslices = ceil_div(n, slice);
-  if (nslices <= 1) {
-    if (n) memcpy(dst, src, n);
-    return;
-  }
-  std::atomic<uint64_t> next{0};
-  run_pool((unsigned)std::min<uint64_t>(nthreads, nslices), [&] {
-    for (uint64_t i; (i = next.fetch_add(1)) < nslices;) {
-      const uint64_t a = i * slice, b = std::min(n, a + slice);
-      memcpy(dst + a, src + a, b - a);
-    }
+  (void)sliced(n, [&](uint64_t a, uint64_t e) {
+    memcpy(dst + a, src + a, e - a);
+    return SF_OK;
   });
 }
-
-// One stage of an explicit block list: blocks [b0, b1), whose bytes all lie
-// in the window [w0, w1) of the caller's buffer.
-struct ListStage {
-  uint64_t b0, b1, w0, w1;
-};
-constexpr uint64_t kListStageMaxBlocks = 1ull << 22;  // keeps a stage's list and digests (~135 MiB) bounded
 
 // sf_index_buffer_blocks: the list is cut into stages of consecutive blocks
 // whose window spans at most ~256 MiB (a larger block is a stage of its own);
@@ -734,16 +656,10 @@ template <typename FillFn>
 int index_list_pipeline(FillFn fill, const uint64_t* offsets, const uint32_t* sizes, uint64_t n, sf_block_sig* out,
                         uint8_t* blocks_hash, const uint8_t* direct = nullptr) {
   const uint64_t target = file_stage_bytes(1);  // ~256 MiB (SF_TEST_STREAM_STAGE_MIB test hook)
-  std::vector<ListStage> stages;
+  std::vector<ListWindow> stages;
   uint64_t max_win = 0, max_blocks = 0;
-  for (uint64_t i = 0; i < n;) {
-    ListStage s{i, i + 1, offsets[i], offsets[i] + sizes[i]};
-    for (i++; i < n && i - s.b0 < kListStageMaxBlocks; i++) {
-      const uint64_t e = std::max(s.w1, offsets[i] + sizes[i]);
-      if (e - s.w0 > target) break;
-      s.w1 = e;
-    }
-    s.b1 = i;
+  for (uint64_t i = 0; i < n; i = stages.back().b1) {
+    const ListWindow s = next_list_window(offsets, sizes, n, i, target);
     max_win = std::max(max_win, s.w1 - s.w0);
     max_blocks = std::max(max_blocks, s.b1 - s.b0);
     stages.push_back(s);
@@ -785,82 +701,62 @@ int index_list_pipeline(FillFn fill, const uint64_t* offsets, const uint32_t* si
   HostLease res;
   hipStream_t* st;
   hipEvent_t* done;
-  void *ddata[2], *pin[2], *dlist[2], *plist[2], *ddig[2], *pdig[2];
-  const uint64_t list_bytes = max_blocks * (sizeof(uint64_t) + sizeof(uint32_t));
+  StageBufs sb[2];
   int rc = res.streams(st, done);
-  for (int i = 0; i < 2 && rc == SF_OK; i++) {
-    rc = res.dev(i, max_win, &ddata[i]);
-    if (rc == SF_OK) rc = res.pin(i, max_win, &pin[i]);
-    if (rc == SF_OK) rc = res.dev(3 + i, max_blocks * 20, &ddig[i]);
-    if (rc == SF_OK) rc = res.pin(3 + i, max_blocks * 20, &pdig[i]);
-    if (rc == SF_OK) rc = res.dev(5 + i, list_bytes, &dlist[i]);
-    if (rc == SF_OK) rc = res.pin(5 + i, list_bytes, &plist[i]);
-  }
+  for (int i = 0; i < 2 && rc == SF_OK; i++)
+    rc = stage_bufs(res, i, max_win, max_blocks, max_blocks * kListEntry, &sb[i]);
   if (rc != SF_OK) return rc;
   sf_host_sha1_stream bh;
   sf_host_sha1_begin(&bh);
-  int64_t stage_of[2] = {-1, -1};  // stage in flight on each buffer set
-  auto harvest = [&](int b) {
-    if (hipEventSynchronize(done[b]) != hipSuccess) return SF_ENODEV;
-    const ListStage& s = stages[(size_t)stage_of[b]];
-    stage_of[b] = -1;
-    const uint8_t* dg = static_cast<const uint8_t*>(pdig[b]);
-    for (uint64_t i = s.b0; i < s.b1; i++) {
-      out[i].offset = offsets[i];
-      out[i].size = sizes[i];
-      memcpy(out[i].sha1, dg + 20 * (i - s.b0), 20);
-    }
-    if (blocks_hash) sf_host_sha1_update(&bh, dg, (s.b1 - s.b0) * 20);
-    return SF_OK;
-  };
-  for (size_t k = 0; k < stages.size() && rc == SF_OK; k++) {
-    const int b = (int)(k & 1);
-    if (stage_of[b] >= 0 && (rc = harvest(b)) != SF_OK) break;  // stage k-2 (k-1 comes later in list order)
-    const ListStage& s = stages[k];
-    const uint64_t nb = s.b1 - s.b0, win = s.w1 - s.w0;
-    const bool direct_k = inplace && region[k] != kFailed && (k == 0 || region[k - 1] != kFailed);
-    if (!direct_k && (rc = fill(static_cast<uint8_t*>(pin[b]), s.w0, s.w1)) != SF_OK) break;
-    uint64_t* lo = static_cast<uint64_t*>(plist[b]);
-    uint32_t* lz = reinterpret_cast<uint32_t*>(lo + nb);
-    for (uint64_t i = 0; i < nb; i++) {
-      lo[i] = offsets[s.b0 + i] - s.w0;
-      lz[i] = sizes[s.b0 + i];
-    }
-    const uint64_t* d_off = static_cast<const uint64_t*>(dlist[b]);
-    const uint32_t* d_sz = reinterpret_cast<const uint32_t*>(d_off + nb);
-    bool copy_ok = true;
-    if (direct_k) {  // a copy lies inside ONE registration: the head (region k-1) apart from the rest
-      const uint8_t* src = direct + s.w0;
-      const uint64_t head = k == 0 ? 0 : std::min<uint64_t>(win, edge(k) - (uintptr_t)src);
-      copy_ok = (!head || hipMemcpyAsync(ddata[b], src, head, hipMemcpyHostToDevice, st[b]) == hipSuccess) &&
-                (win == head || hipMemcpyAsync(static_cast<uint8_t*>(ddata[b]) + head, src + head, win - head,
-                                               hipMemcpyHostToDevice, st[b]) == hipSuccess);
-    } else if (win) {
-      copy_ok = hipMemcpyAsync(ddata[b], pin[b], win, hipMemcpyHostToDevice, st[b]) == hipSuccess;
-    }
-    if (!copy_ok || hipMemcpyAsync(dlist[b], plist[b], nb * (sizeof(uint64_t) + sizeof(uint32_t)),
-                                   hipMemcpyHostToDevice, st[b]) != hipSuccess) {
-      rc = SF_ENODEV;
-      break;
-    }
-    if (inplace && k + 1 < nst) lock_region(k + 1);  // one region ahead of the copies that read it
-    // every block was checked to lie in [0, len), so in its window: no status word
-    if ((rc = launch_table(ddata[b], win, d_off, d_sz, nb, ddig[b], nullptr, st[b])) != SF_OK) break;
-    if (hipMemcpyAsync(pdig[b], ddig[b], nb * 20, hipMemcpyDeviceToHost, st[b]) != hipSuccess ||
-        hipEventRecord(done[b], st[b]) != hipSuccess) {
-      rc = SF_ENODEV;
-      break;
-    }
-    stage_of[b] = (int64_t)k;
-  }
-  // the (at most two) stages still in flight, in list order
-  int order[2] = {0, 1};
-  if (stage_of[0] >= 0 && stage_of[1] >= 0 && stage_of[1] < stage_of[0]) std::swap(order[0], order[1]);
-  for (int b : order)
-    if (stage_of[b] >= 0) {
-      const int r = harvest(b);
-      if (rc == SF_OK) rc = r;
-    }
+  rc = two_stage(
+      nst,
+      [&](uint64_t k, int b) {
+        const ListWindow& s = stages[k];
+        const uint64_t nb = s.b1 - s.b0, win = s.w1 - s.w0;
+        const bool direct_k = inplace && region[k] != kFailed && (k == 0 || region[k - 1] != kFailed);
+        if (!direct_k)
+          if (const int r = fill(static_cast<uint8_t*>(sb[b].pin), s.w0, s.w1)) return r;
+        uint64_t* lo = static_cast<uint64_t*>(sb[b].paux);
+        uint32_t* lz = reinterpret_cast<uint32_t*>(lo + nb);
+        for (uint64_t i = 0; i < nb; i++) {
+          lo[i] = offsets[s.b0 + i] - s.w0;
+          lz[i] = sizes[s.b0 + i];
+        }
+        const uint64_t* d_off = static_cast<const uint64_t*>(sb[b].daux);
+        const uint32_t* d_sz = reinterpret_cast<const uint32_t*>(d_off + nb);
+        bool copy_ok = true;
+        if (direct_k) {  // a copy lies inside ONE registration: the head (region k-1) apart from the rest
+          const uint8_t* src = direct + s.w0;
+          const uint64_t head = k == 0 ? 0 : std::min<uint64_t>(win, edge(k) - (uintptr_t)src);
+          copy_ok = (!head || hipMemcpyAsync(sb[b].ddata, src, head, hipMemcpyHostToDevice, st[b]) == hipSuccess) &&
+                    (win == head || hipMemcpyAsync(static_cast<uint8_t*>(sb[b].ddata) + head, src + head, win - head,
+                                                   hipMemcpyHostToDevice, st[b]) == hipSuccess);
+        } else if (win) {
+          copy_ok = hipMemcpyAsync(sb[b].ddata, sb[b].pin, win, hipMemcpyHostToDevice, st[b]) == hipSuccess;
+        }
+        if (!copy_ok ||
+            hipMemcpyAsync(sb[b].daux, sb[b].paux, nb * kListEntry, hipMemcpyHostToDevice, st[b]) != hipSuccess)
+          return SF_ENODEV;
+        if (inplace && k + 1 < nst) lock_region(k + 1);  // one region ahead of the copies that read it
+        // every block was checked to lie in [0, len), so in its window: no status word
+        if (const int r = launch_table(sb[b].ddata, win, d_off, d_sz, nb, sb[b].ddig, nullptr, st[b])) return r;
+        if (hipMemcpyAsync(sb[b].pdig, sb[b].ddig, nb * 20, hipMemcpyDeviceToHost, st[b]) != hipSuccess ||
+            hipEventRecord(done[b], st[b]) != hipSuccess)
+          return SF_ENODEV;
+        return SF_OK;
+      },
+      [&](uint64_t k, int b) {
+        if (hipEventSynchronize(done[b]) != hipSuccess) return SF_ENODEV;
+        const ListWindow& s = stages[k];
+        const uint8_t* dg = static_cast<const uint8_t*>(sb[b].pdig);
+        for (uint64_t i = s.b0; i < s.b1; i++) {
+          out[i].offset = offsets[i];
+          out[i].size = sizes[i];
+          memcpy(out[i].sha1, dg + 20 * (i - s.b0), 20);
+        }
+        if (blocks_hash) sf_host_sha1_update(&bh, dg, (s.b1 - s.b0) * 20);
+        return SF_OK;
+      });
   if (rc == SF_OK && blocks_hash) sf_host_sha1_final(&bh, blocks_hash);
   return rc;
 }
@@ -904,46 +800,6 @@ bool same_stamp(const sf_file_stamp& a, const sf_file_stamp& b) {
 
 namespace {
 
-// body(stamp, mode) between two stamps of fd.  A read that came up short (the
-// file shrank: SF_EIO) or a complete one over a file whose stamp moved is
-// SF_EAGAIN; other results (argument errors, SF_ENOSPC, device errors) pass.
-template <typename Body>
-int stamped(int fd, const sf_file_stamp* expect, Body body) {
-  sf_file_stamp before{}, after{};
-  mode_t mode = 0;
-  if (!stamp_of(fd, &before, &mode)) return SF_EIO;
-  if (expect && !same_stamp(before, *expect)) return SF_EAGAIN;
-  const int rc = body(before, mode);
-  if (rc != SF_OK && rc != SF_EIO) return rc;
-  if (!stamp_of(fd, &after, nullptr)) return SF_EIO;
-  return same_stamp(before, after) ? rc : SF_EAGAIN;
-}
-
-// Bytes [w0, w0 + m) of fd into dst: pread slices on the reader threads.  A
-// short read (the file shrank after the list was made) is SF_EIO.
-int pread_window(int fd, uint8_t* dst, uint64_t w0, uint64_t m) {
-  const unsigned nthreads = std::max(1u, std::min(io_threads(), std::thread::hardware_concurrency()));
-  const uint64_t slice = std::max<uint64_t>(4ull << 20, ceil_div(m, nthreads));
-  const uint64_t nslices = ceil_div(m, slice);
-  std::atomic<uint64_t> next{0};
-  std::atomic<int> frc{SF_OK};
-  run_pool((unsigned)std::min<uint64_t>(nthreads, std::max<uint64_t>(nslices, 1)), [&] {
-    for (uint64_t k; (k = next.fetch_add(1)) < nslices && frc.load() == SF_OK;) {
-      const uint64_t a = k * slice, e = std::min(m, a + slice);
-      for (uint64_t got = a; got < e;) {
-        const ssize_t r = pread(fd, dst + got, e - got, (off_t)(w0 + got));
-        if (r < 0 && errno == EINTR) continue;
-        if (r <= 0) {
-          frc.store(SF_EIO);
-          break;
-        }
-        got += (uint64_t)r;
-      }
-    }
-  });
-  return frc.load();
-}
-
 void empty_blocks_hash(uint8_t* blocks_hash) {  // compute_blocks_hash of no blocks: SHA-1("")
   if (!blocks_hash) return;
   sf_host_sha1_stream bh;
@@ -955,17 +811,14 @@ void empty_blocks_hash(uint8_t* blocks_hash) {  // compute_blocks_hash of no blo
 // against len, then windows pread into the pinned stages of the list pipeline.
 int index_fd_list(int fd, uint64_t len, const uint64_t* offsets, const uint32_t* sizes, uint64_t n,
                   sf_block_sig* out, uint8_t* blocks_hash) {
-  for (uint64_t i = 0; i < n; i++) {
-    if (offsets[i] > len || sizes[i] > len - offsets[i]) return SF_ERANGE;
-    if (i && offsets[i] < offsets[i - 1]) return SF_EINVAL;
-  }
+  if (const int rc = check_list(len, offsets, sizes, n)) return rc;
   if (n == 0) {
     empty_blocks_hash(blocks_hash);
     return SF_OK;
   }
   uint64_t window = 0;
   auto fill = [&](uint8_t* dst, uint64_t w0, uint64_t w1) {
-    const int r = pread_window(fd, dst, w0, w1 - w0);
+    const int r = read_sliced(fd, dst, w0, w1 - w0);
     read_hook(window++);
     return r;
   };
@@ -982,16 +835,9 @@ static int sf_index_buffer_blocks_body(const uint8_t* data, uint64_t len, const 
   if (len && !data) return SF_EINVAL;
   // The whole list is checked before any byte moves (the device form zeroes
   // an out-of-range block's digest instead; a host caller gets the error).
-  for (uint64_t i = 0; i < n; i++) {
-    if (offsets[i] > len || sizes[i] > len - offsets[i]) return SF_ERANGE;
-    if (i && offsets[i] < offsets[i - 1]) return SF_EINVAL;
-  }
+  if (const int rc = check_list(len, offsets, sizes, n)) return rc;
   if (n == 0) {
-    if (blocks_hash) {  // compute_blocks_hash of no blocks: SHA-1 of the empty string
-      sf_host_sha1_stream bh;
-      sf_host_sha1_begin(&bh);
-      sf_host_sha1_final(&bh, blocks_hash);
-    }
+    empty_blocks_hash(blocks_hash);
     return SF_OK;
   }
   auto fill = [&](uint8_t* dst, uint64_t w0, uint64_t w1) {

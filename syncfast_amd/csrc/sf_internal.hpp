@@ -8,6 +8,7 @@
 //   sf_files.cpp  sf_index_files, the many-file pipeline;
 //   sf_fds.cpp    sf_index_fds_blocks, the default mode over many files;
 //   sf_multi.cpp  one process, N devices;
+//   sf_stage.cpp  what those pipelines share (sf_stage.hpp: the stage driver);
 //   sf_pool.cpp   the host worker threads of every pipeline (run_pool);
 //   sf_zpaq.cpp   the reference's ZPAQ chunker on the host;
 //   sf_cdc.hip    the same boundaries cut on the device (its own kernels).
@@ -32,6 +33,7 @@
 #include <vector>
 
 #include "../../include/syncfast_amd.h"
+#include "sf_stage.hpp"
 
 // Internal status of the in-place route (never returned through the C-ABI):
 // the caller's pages could not be page-locked, take the staged route.
@@ -89,21 +91,6 @@ inline int guarded(F&& body) noexcept {
   } catch (...) {
     return SF_EIO;
   }
-}
-
-// Runs `worker` on the calling thread and on up to nthreads-1 of the
-// library's kept helper threads (sf_pool.cpp).  The workers share an atomic
-// work counter, so helpers busy elsewhere or a thread the system refuses only
-// lower the parallelism.  Returns when every helper that started the worker
-// has finished it; an exception from any of them is rethrown here.
-void run_pool_fn(unsigned nthreads, const std::function<void()>& worker);
-template <typename F>
-inline void run_pool(unsigned nthreads, F&& worker) {
-  if (nthreads <= 1) {
-    worker();
-    return;
-  }
-  run_pool_fn(nthreads, std::function<void()>(std::ref(worker)));
 }
 
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
@@ -167,9 +154,7 @@ constexpr int kMaxDevices = 64;
 struct HostRes {
   hipStream_t s[2] = {nullptr, nullptr};
   hipEvent_t ev[2] = {nullptr, nullptr};
-  // Slots (device and pinned alike): 0, 1 = the two stages; 2 = the digest
-  // table of one file; 3, 4 = the digest tables of sf_index_files' two
-  // stages; 5, 6 = their blocks_hash arrays; 7 = unused.
+  // Slots (device and pinned alike): enum Slot in sf_stage.hpp names them; 7 = unused.
   static constexpr int kSlots = 8;
   void* dev[kSlots] = {};
   uint64_t dev_cap[kSlots] = {};
@@ -274,12 +259,6 @@ class HostLease {
   HostRes* own_ = nullptr;
   std::vector<void*> tmp_dev_, tmp_pin_;
 };
-
-// fstat(fd) as a stamp (and the file's mode); false if fstat fails.  Two
-// stamps match when dev, ino, size and mtime are equal and, unless the link
-// count changed, ctime too (include/syncfast_amd.h, sf_file_stamp).
-bool stamp_of(int fd, sf_file_stamp* s, mode_t* mode);
-bool same_stamp(const sf_file_stamp& a, const sf_file_stamp& b);
 
 // Fixed tiling of bytes [base, base + len) of the regular file open on fd
 // (base a multiple of bs) through the staged pread pipeline (sf_host.cpp) on

@@ -263,3 +263,13 @@ def test_concurrent_in_place_calls_on_shared_pages(gpu):
     for t in th:
         t.join(timeout=120)
     assert not errors, errors
+
+
+@pytest.mark.parametrize("stages", [1, 2, 3, 4])
+def test_cdc_like_stage_counts(gpu, small_stages, stages):
+    """A CDC-like list over (stages - 1) MiB + 1 bytes in 1 MiB stages: one
+    stage in flight at the end, two, and each parity of the last one."""
+    n = ((stages - 1) << 20) + 1
+    data = oracle.splitmix_bytes(n, 0x5EED0100 + stages)
+    offs, sizes = _cdc_like(np.random.default_rng(n), n)
+    _check(data, offs, sizes)

@@ -273,3 +273,32 @@ def test_index_file_of_a_file_appended_on_every_window(gpu, tmp_path, small_stag
     dig, wbh = _want(data, offs, sizes)
     assert [h.bytes for h, _o, _s in rows] == [bytes(d) for d in dig]
     assert bh.bytes == wbh and total >= 3 * MIB + 5
+
+
+@pytest.mark.parametrize("stages", [1, 2, 3, 4])
+def test_stage_counts_equal_oracle(gpu, tmp_path, small_stages, stages):
+    """1 MiB stages over (stages - 1) MiB + 1 bytes -- one stage in flight at
+    the end, two, and each parity of the last one -- through sf_index_fd_fixed,
+    sf_index_file and, with a CDC-like list, sf_index_fd_blocks."""
+    p = tmp_path / "f"
+    data = oracle.splitmix_bytes((stages - 1) * MIB + 1, 6400 + stages).tobytes()
+    p.write_bytes(data)
+    offs, sizes, want = oracle.index_fixed(np.frombuffer(data, np.uint8), 4096)
+    windows = []
+    _lib.set_read_hook(windows.append)
+    with open(p, "rb") as f:
+        rows, bh = host.index_fd_fixed(f.fileno(), 4096, host.file_stamp(f.fileno()))
+    _lib.set_read_hook(None)
+    assert windows == list(range(stages))  # one window per stage, numbered in order
+    assert np.array_equal(rows["sha1"], want) and bh == oracle.blocks_hash(want)
+    assert np.array_equal(rows["offset"], offs) and np.array_equal(rows["size"], sizes)
+    rows, bh = host.index_file(p, 4096)
+    assert np.array_equal(rows["sha1"], want) and bh == oracle.blocks_hash(want)
+    assert np.array_equal(rows["offset"], offs) and np.array_equal(rows["size"], sizes)
+    sizes = _cdc_like_sizes(len(data), 6410 + stages)
+    offs = _offs(sizes)
+    with open(p, "rb") as f:
+        rows, bh = host.index_fd_blocks(f.fileno(), offs, sizes, host.file_stamp(f.fileno()))
+    dig, wbh = _want(data, offs, sizes)
+    assert np.array_equal(rows["sha1"], dig) and bh == wbh
+    assert np.array_equal(rows["offset"], offs) and np.array_equal(rows["size"], sizes)

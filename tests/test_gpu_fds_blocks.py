@@ -523,3 +523,16 @@ def test_index_path_large_file_among_small_files(gpu, tmp_path):
         assert fids == sorted(fids)
     finally:
         lib.sf_zpaq_standin_ops_free(ops)
+
+
+@pytest.mark.parametrize("nfiles", [1, 2, 3, 4])
+def test_stage_counts_equal_oracle(gpu, tmp_path, nfiles):
+    """Files of ~0.7 MiB in 1 MiB stages -- a stage each, so 1 to 4 stages: one
+    in flight at the end, two, and each parity of the last one -- and an empty
+    file among them."""
+    lens = [700 * KIB + 13 * k for k in range(nfiles)]
+    lens.insert(len(lens) // 2, 0)
+    files = _tree(tmp_path, lens, 7600 + nfiles)
+    rows, first, hashes, status = _run(files, stage_bytes=1 * MIB)
+    assert int(first[-1]) == sum(len(s) for *_r, s in files)
+    _check(files, rows, first, hashes, status)

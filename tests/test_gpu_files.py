@@ -112,3 +112,16 @@ def test_index_files_reports_the_failing_file(gpu, tmp_path):
     assert e.value.code == -5 and str(tmp_path) in str(e.value)
     rows, first, fh = host.index_files(paths, 4096)  # and the call after an error is clean
     _check(paths, [100, 5000, 7], 3100, 4096, rows, first, fh)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("nfiles", [1, 2, 3, 4])
+def test_index_files_stage_counts(gpu, tmp_path, nfiles):
+    """Files of ~0.7 MiB in 1 MiB stages -- a stage each, so 1 to 4 stages: one
+    in flight at the end, two, and each parity of the last one -- and an empty
+    file among them."""
+    sizes = [700 * 1024 + 13 * k for k in range(nfiles)]
+    sizes.insert(len(sizes) // 2, 0)
+    paths = _write(tmp_path, sizes, 7700 + nfiles)
+    rows, first, fh = host.index_files(paths, 4096, stage_bytes=1 << 20)
+    _check(paths, sizes, 7700 + nfiles, 4096, rows, first, fh)

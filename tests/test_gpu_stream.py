@@ -124,3 +124,19 @@ def test_index_fd_bad_descriptor(gpu):
     os.close(w)
     with pytest.raises(SfError):
         host.index_fd(r, 4096)
+
+
+@pytest.mark.parametrize("stages", [1, 2, 3, 4])
+def test_index_fd_pipe_stage_counts(gpu, stages, knobs):
+    """1 MiB stages over (stages - 1) MiB + 1 bytes from a pipe: one stage in
+    flight at the end, two, and each parity of the last one."""
+    knobs.set("SF_TEST_STREAM_STAGE_MIB", 1)
+    data = oracle.splitmix_bytes(((stages - 1) << 20) + 1, 760 + stages)
+    r, w = os.pipe()
+    th = _writer(w, data.tobytes())
+    try:
+        rows, bh = host.index_fd(r, 4096)
+    finally:
+        th.join(timeout=60)
+        os.close(r)
+    _check(rows, bh, data, 4096)

@@ -1,5 +1,7 @@
 """Wire emission of signature tables (src/sync/ssh/proto.rs)."""
 import ctypes
+import os
+
 import numpy as np
 import pytest
 import torch
@@ -205,3 +207,51 @@ def test_blocks_to_fd_streams_the_device_run(gpu, tmp_path, chunk, knobs):
     with open(p, "wb") as f:
         got = wire.blocks_to_fd(dig, sizes, f.fileno())
     assert got == len(want) and p.read_bytes() == want
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("nblocks", [1, 3, 5, 7])
+def test_fd_routes_chunk_counts(gpu, tmp_path, knobs, nblocks):
+    """Chunks of 2 messages over 1, 3, 5 and 7 blocks: 1 to 4 chunks -- one in
+    flight at the end, two, and each parity of the last one -- through both
+    descriptor routes, against the messages written one by one."""
+    knobs.set("SF_TEST_WIRE_CHUNK", 2)
+    bs = 4096
+    n = bs * (nblocks - 1) + 7
+    data = oracle.splitmix_bytes(n, 8800 + nblocks)
+    dig = device.index_device(torch.from_numpy(data.copy()).to(gpu), bs)
+    _, sizes, want_d = oracle.index_fixed(data, bs)
+    want = b"".join(wire.write_message("FileBlock", bytes(dd), int(sz)) for dd, sz in zip(want_d, sizes))
+    p = tmp_path / "fixed.bin"
+    with open(p, "wb") as f:
+        assert wire.file_blocks_to_fd(dig, bs, n, f.fileno()) == len(want)
+    assert p.read_bytes() == want
+    p = tmp_path / "list.bin"
+    with open(p, "wb") as f:
+        assert wire.blocks_to_fd(dig, torch.from_numpy(sizes.astype(np.int32)).to(gpu), f.fileno()) == len(want)
+    assert p.read_bytes() == want
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("route", ["fixed", "list"])
+def test_fd_routes_write_nothing_after_a_failed_write(gpu, knobs, route):
+    """/dev/full refuses the first chunk: SF_EIO, and no later chunk is
+    flushed -- *n_written stays 0."""
+    from syncfast_amd import _lib
+    knobs.set("SF_TEST_WIRE_CHUNK", 2)
+    bs, nblocks = 4096, 7
+    n = bs * (nblocks - 1) + 7
+    dig = device.index_device(torch.from_numpy(oracle.splitmix_bytes(n, 8900).copy()).to(gpu), bs)
+    sizes = torch.full((nblocks,), bs, dtype=torch.int32, device=gpu)
+    sizes[-1] = 7
+    torch.cuda.synchronize()
+    out = ctypes.c_uint64(99)
+    fd = os.open("/dev/full", os.O_WRONLY)
+    try:
+        if route == "fixed":
+            rc = _lib.lib().sf_wire_file_blocks_fd(dig.data_ptr(), nblocks, bs, n, fd, ctypes.byref(out), None)
+        else:
+            rc = _lib.lib().sf_wire_blocks_fd(dig.data_ptr(), sizes.data_ptr(), nblocks, fd, ctypes.byref(out), None)
+    finally:
+        os.close(fd)
+    assert rc == _lib.SF_EIO and out.value == 0
