@@ -240,6 +240,65 @@ int sf_wire_file_blocks_fd(const void *d_digests, uint64_t n_blocks, uint32_t bl
 int sf_wire_blocks_fd(const void *d_digests, const uint32_t *d_sizes, uint64_t n_blocks, int fd,
                       uint64_t *n_written, void *stream);
 
+/* ------------------------------ receiving a FILE_BLOCK run, on the device ---- */
+
+/* Why the parse of a run stopped (what stands after the last whole message). */
+enum {
+    SF_WIRE_END = 0,        /* the run ends with the buffer */
+    SF_WIRE_INCOMPLETE = 1, /* the start of a message: more bytes could complete it */
+    SF_WIRE_OTHER = 2,      /* a complete command line of another message (FILE_END, ...):
+                               the caller's parser takes over there */
+    SF_WIRE_MALFORMED = 3   /* the reference parser would raise there */
+};
+
+/* The inverse of sf_wire_blocks_device: the longest prefix of whole FILE_BLOCK
+ * messages of d_wire[0, n_bytes), as the reference parser reads them
+ * (src/sync/ssh/proto.rs:189-477): message i = "FILE_BLOCK\n" + 20 digest
+ * bytes + "\n" + a size field + "\n", the field what usize::from_str takes
+ * ("+"? [0-9]+, leading zeros allowed) in at most 15 bytes.  Digest i goes to
+ * d_digests + 20 * i (4-B aligned, the table sf_block_set_lookup takes), the
+ * size to d_sizes[i].  *n_out = the messages, *consumed = their bytes, *stop =
+ * SF_WIRE_* for what stands at d_wire + *consumed: nothing, a message's start
+ * (a command line under 20 bytes with no newline included), one of the eight
+ * other commands' complete line (whatever follows it), or bytes the parser
+ * rejects (an unknown or unterminated command, an unterminated digest or
+ * size, an invalid size).  Every byte position is tested for a whole message
+ * in parallel, and the positions that chain from byte 0 are the messages
+ * (sf_recv.hip); a digest that forges a message start inside
+ * a message is noticed, and the run is then copied back and parsed on the
+ * host, serially -- the result is the reference parser's for any input.  d_wire needs no alignment.
+ * Unlike the reference (usize), sizes are uint32 here as in every other entry
+ * point: a size above 2^32 - 1 gives SF_ERANGE.  SF_ENOSPC with *n_out = the
+ * need (the first cap entries written) when cap is too small or an output is
+ * NULL (a query).  n_bytes == 0 gives 0 messages; n_bytes <= 2^38.
+ * Scratch: n_bytes / 3 from the library's stream-ordered pool.  Blocking. */
+int sf_wire_parse_blocks_device(const void *d_wire, uint64_t n_bytes, void *d_digests /* 4-B aligned */,
+                                uint32_t *d_sizes, uint64_t cap, uint64_t *n_out,
+                                uint64_t *consumed, int *stop, void *stream);
+
+/* The body of the sink's GetFiles state for one run (src/sync/fs.rs:461-478)
+ * in one call: sf_wire_parse_blocks_device, then d_offsets[i] = base_offset +
+ * d_sizes[0] + ... + d_sizes[i - 1] (the running offset of fs.rs:477, a 64-bit
+ * scan), then sf_block_set_lookup of the digests into d_rows (the row to copy
+ * from, or -1: add_missing_block) unless set is NULL.  *end_offset = the
+ * offset after the last message -- what FILE_END passes to
+ * set_file_size_and_compute_blocks_hash (fs.rs:480), and the base_offset of
+ * the next call when a run arrives in pieces (the unconsumed tail + the new
+ * bytes).  cap entries per output; SF_ENOSPC with *n_out = the need when it
+ * is smaller or an output is NULL.  Blocking. */
+int sf_receive_blocks_device(const sf_block_set *set /* NULL: no lookup */, const void *d_wire, uint64_t n_bytes,
+                             uint64_t base_offset, void *d_digests, uint32_t *d_sizes, uint64_t *d_offsets,
+                             int64_t *d_rows, uint64_t cap, uint64_t *n_out, uint64_t *consumed, int *stop,
+                             uint64_t *end_offset, void *stream);
+
+/* The same from host memory: the run goes to HBM through the pinned stages,
+ * out[i] = {offset, size, digest} and src_rows[i] (may be NULL without a
+ * set) come back.  When the host parse is needed it reads the caller's own
+ * bytes: nothing is copied back.  Blocking. */
+int sf_receive_blocks_buffer(const sf_block_set *set, const void *wire /* host */, uint64_t n_bytes,
+                             uint64_t base_offset, sf_block_sig *out, int64_t *src_rows, uint64_t cap,
+                             uint64_t *n_out, uint64_t *consumed, int *stop, uint64_t *end_offset);
+
 /* Deterministic synthetic input (bench / tests): bytes [start, start+len)
  * of the splitmix64 stream with this seed. */
 int sf_fill_splitmix_device(void *d_out, uint64_t len, uint64_t seed, uint64_t start, void *stream);

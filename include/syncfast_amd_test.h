@@ -80,6 +80,13 @@ int sf_test_xcd_litmus(int mode, uint32_t out[8]);
  * them.  Host only; not synchronised with cuts in flight. */
 int sf_test_zpaq_device_stats(uint64_t out[4]);
 
+/* What the last FILE_BLOCK parse of this process did (sf_wire_parse_blocks_device
+ * and the calls built on it): out[0] the candidate positions the device found
+ * (0 when the parse was forced to the host), out[1] the messages, out[2] 1 if
+ * the host fallback ran (a forged message start, or SF_TEST_WIRE_PARSE_HOST),
+ * out[3] reserved (0).  Host only; not synchronised with calls in flight. */
+int sf_test_wire_parse_stats(uint64_t out[4]);
+
 #ifdef __cplusplus
 }
 #endif

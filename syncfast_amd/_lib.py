@@ -24,6 +24,9 @@ SF_ENOSPC = -28
 SF_ERANGE = -34
 SF_ETIMEDOUT = -110
 
+# Why a FILE_BLOCK parse stopped (sf_wire_parse_blocks_device)
+SF_WIRE_END, SF_WIRE_INCOMPLETE, SF_WIRE_OTHER, SF_WIRE_MALFORMED = 0, 1, 2, 3
+
 HASH_DIGEST_LEN = 20
 MAX_BLOCK_SIZE = 32 << 20
 
@@ -39,12 +42,14 @@ EXPORTED = (
     "sf_blocks_hash", "sf_blocks_hash_sigs", "sf_sha1_host",
     "sf_block_set_build", "sf_block_set_lookup", "sf_block_set_free",
     "sf_zpaq_cut_buffer", "sf_zpaq_chunker_ops", "sf_cut_device_zpaq", "sf_index_device_zpaq", "sf_index_fd_zpaq",
+    "sf_wire_parse_blocks_device", "sf_receive_blocks_device", "sf_receive_blocks_buffer",
 )
 # Test hooks (include/syncfast_amd_test.h): knobs latched at load, route counters,
 # the explicit-list processing order.
 EXPORTED_TEST = ("sf_test_set_knob", "sf_test_get_knob", "sf_test_get_stat", "sf_test_table_order",
                  "sf_test_table_order_bits",
-                 "sf_test_set_read_hook", "sf_test_xcd_litmus", "sf_test_multi_plan", "sf_test_zpaq_device_stats")
+                 "sf_test_set_read_hook", "sf_test_xcd_litmus", "sf_test_multi_plan", "sf_test_zpaq_device_stats",
+                 "sf_test_wire_parse_stats")
 
 
 class SfError(OSError):
@@ -150,6 +155,12 @@ def _declare(L: ctypes.CDLL) -> None:
     L.sf_index_device_zpaq.argtypes = [vp, u64, u32, u32, vp, vp, vp, u64, pu64, vp, vp]
     L.sf_index_fd_zpaq.argtypes = [i32, vp, u32, u32, ctypes.POINTER(ctypes.POINTER(BlockSig)), pu64, vp]
     L.sf_test_zpaq_device_stats.argtypes = [vp]
+    pint = ctypes.POINTER(ctypes.c_int)
+    L.sf_wire_parse_blocks_device.argtypes = [vp, u64, vp, vp, u64, pu64, pu64, pint, vp]
+    L.sf_receive_blocks_device.argtypes = [vp, vp, u64, u64, vp, vp, vp, vp, u64, pu64, pu64, pint, pu64, vp]
+    L.sf_receive_blocks_buffer.argtypes = [vp, vp, u64, u64, ctypes.POINTER(BlockSig), vp, u64, pu64, pu64, pint,
+                                           pu64]
+    L.sf_test_wire_parse_stats.argtypes = [vp]
     pi64 = ctypes.POINTER(ctypes.c_int64)
     L.sf_test_set_knob.argtypes = [ctypes.c_char_p, ctypes.c_int64, pi64]
     L.sf_test_get_knob.argtypes = [ctypes.c_char_p, pi64]

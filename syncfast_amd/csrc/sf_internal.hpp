@@ -11,7 +11,9 @@
 //   sf_stage.cpp  what those pipelines share (sf_stage.hpp: the stage driver);
 //   sf_pool.cpp   the host worker threads of every pipeline (run_pool);
 //   sf_zpaq.cpp   the reference's ZPAQ chunker on the host;
-//   sf_cdc.hip    the same boundaries cut on the device (its own kernels).
+//   sf_cdc.hip    the same boundaries cut on the device (its own kernels);
+//   sf_recv.hip   FILE_BLOCK runs parsed on the device (its own kernels; the
+//                 host parser is sf_wire_parse.hpp).
 // The .cpp files use only the HIP runtime API (no kernels), so they build
 // with the host compiler.
 #pragma once
@@ -54,7 +56,8 @@ enum Knob {
   K_IO_THREADS, K_INPLACE_MIN_MIB, K_INPLACE_SERIAL, K_FADVISE, K_NO_HOSTREG, K_TABLE_CLASS_BITS, K_TRACE,
   K_BATCH_FUSED,
   K_TEST_INPLACE_FAIL_AT, K_TEST_WIRE_CHUNK, K_TEST_STREAM_STAGE_MIB, K_TEST_LAUNCH_MAX_BLOCKS, K_TEST_TABLE_SORT,
-  K_TEST_MULTI_SELF_GATHER, K_TEST_CUT_WINDOW_MIB, K_TEST_STREAM_POOL, K_TEST_ZPAQ_WINDOW, K_COUNT
+  K_TEST_MULTI_SELF_GATHER, K_TEST_CUT_WINDOW_MIB, K_TEST_STREAM_POOL, K_TEST_ZPAQ_WINDOW, K_TEST_WIRE_PARSE_HOST,
+  K_COUNT
 };
 struct KnobDef {
   const char* env;

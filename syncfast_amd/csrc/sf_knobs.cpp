@@ -35,6 +35,7 @@ const KnobDef kKnobDefs[K_COUNT] = {
     {"SF_TEST_CUT_WINDOW_MIB", 0},      // K_TEST_CUT_WINDOW_MIB: sf_index_fd_cut's window (0 = 512 MiB)
     {"SF_TEST_STREAM_POOL", 1},         // K_TEST_STREAM_POOL: scratch pool (1 own, keeps blocks; 0 / 3 known wrong)
     {"SF_TEST_ZPAQ_WINDOW", 0},         // K_TEST_ZPAQ_WINDOW: sf_index_fd_zpaq's window in bytes (0 = 512 MiB)
+    {"SF_TEST_WIRE_PARSE_HOST", 0},     // K_TEST_WIRE_PARSE_HOST: 1 = FILE_BLOCK runs are parsed by the host fallback
 };
 
 std::atomic<int64_t> g_knob[K_COUNT];

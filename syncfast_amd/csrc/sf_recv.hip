@@ -1,0 +1,518 @@
+// sf_recv.hip -- the receiving side of a FILE_BLOCK run on the device
+// (include/syncfast_amd.h: sf_wire_parse_blocks_device, sf_receive_blocks_device,
+// sf_receive_blocks_buffer): the inverse of sf_wire.hip.  Its own translation
+// unit: the other kernels' code objects stay as they are.
+//
+// A message is "FILE_BLOCK\n" + 20 raw digest bytes + "\n" + a size field of
+// 1 to 15 bytes + "\n" (34 to 48 bytes; sf_wire_parse.hpp has the rules).
+// Digests are arbitrary bytes, so a message start cannot be told from a digest
+// that happens to hold the same bytes: message i starts where message i - 1
+// ends, which is serial.  What is parallel:
+//
+//   candidates  every byte position p is tested (a lane takes 16 of them): p
+//               is a candidate when a whole, valid message stands there
+//               (block_message, the same function the host parser uses).
+//               Every true message start is one; a digest may forge others.
+//               64 positions' flags are one word of a bitmap and one count.
+//   scan        rocprim inclusive scan of the counts: the candidates before
+//               each word, i.e. every candidate's index in position order.
+//   chain       one lane per word, for each of its candidates at p with
+//               length L: the link is good when p + L is a candidate and no
+//               candidate lies in (p, p + L).  The first candidate whose link
+//               is not good is the last message of the prefix that chains
+//               from byte 0 (atomicMin on its index + 1, with a bit that says
+//               whether a candidate lay inside it); candidate 0 not at byte 0
+//               is an empty prefix.
+//   extract     one lane per word again: candidates below that index are the
+//               messages; lane writes digest, size and, for the last one, the
+//               end offset E.
+//
+// With no candidate strictly inside [0, E) off the chain, the candidates in
+// [0, E) ARE the chain, E is not a candidate, and the reference parser --
+// which reads message after message from byte 0 -- reads exactly that prefix
+// and stops at E.  A candidate inside the last chained message (the only
+// place one can hide: the chain check stops at the first) means a digest
+// forged a message start; then the call parses the run on the host, serially
+// and exactly (parse_run).  Every dependency is a kernel boundary; no lane
+// waits for another; every loop is bounded by a message's 48 bytes or a
+// word's 64 bits.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <string.h>
+
+#include <memory>
+
+#include <rocprim/device/device_scan.hpp>
+#include <rocprim/iterator/transform_iterator.hpp>
+
+#include "sf_internal.hpp"
+#include "sf_stage.hpp"
+#include "sf_wire_parse.hpp"
+#include "../../include/syncfast_amd_test.h"
+
+namespace {
+
+constexpr uint64_t kMaxRun = 1ull << 38;  // bytes per call: every grid stays far below 2^31 workgroups
+
+// What the host reads back, in one copy.
+struct Result {
+  unsigned long long first_bad;  // ((index of the prefix's last message + 1) << 1) | (no candidate inside it)
+  unsigned long long cand, msgs, end;
+  uint32_t too_large, pad;
+};
+
+constexpr uint32_t kPerLane = 16;  // byte positions per lane of the candidates kernel
+
+// 0x80 in exactly the bytes of v that equal c
+__device__ __forceinline__ uint32_t bytes_equal(uint32_t v, uint32_t c) {
+  const uint32_t x = v ^ (c * 0x01010101u);
+  return ~(((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x | 0x7F7F7F7Fu);
+}
+
+// One lane per 16 byte positions [p0, p0 + 16): their bytes come as aligned
+// dwords (data itself needs no alignment: the five dwords that hold them are
+// shifted into place) where all five lie inside [data, data + n), else byte by
+// byte, so nothing outside the run is read.  Only a position that holds 'F'
+// is looked at further.  Four lanes' flags make one word of the bitmap.
+__global__ void __launch_bounds__(256) recv_candidates_kernel(const uint8_t* __restrict__ data, uint64_t n,
+                                                              unsigned long long* __restrict__ words,
+                                                              uint32_t* __restrict__ counts) {
+  const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const uint64_t p0 = g * kPerLane;
+  uint32_t w[4] = {0, 0, 0, 0}, mask = 0;
+  if (p0 < n) {
+    const uint32_t a = (uint32_t)(reinterpret_cast<uintptr_t>(data) & 3u);  // the same for every lane: p0 is a multiple of 16
+    if (p0 >= a && p0 - a + kPerLane + 4 <= n) {
+      const uint32_t* q = reinterpret_cast<const uint32_t*>(data + p0 - a);
+      const uint32_t d[5] = {q[0], q[1], q[2], q[3], a ? q[4] : 0u};
+#pragma unroll
+      for (int j = 0; j < 4; j++) w[j] = __funnelshift_r(d[j], d[j + 1], 8 * a);
+    } else {
+      const uint32_t m = n - p0 < kPerLane ? (uint32_t)(n - p0) : kPerLane;
+      for (uint32_t k = 0; k < m; k++) w[k >> 2] |= (uint32_t)data[p0 + k] << (8 * (k & 3));
+    }
+    // the positions that hold 'F', one after the other: most lanes have one
+    // (a message is about 37 bytes), so the wave tests one position at a time
+    unsigned long long f0 = bytes_equal(w[0], 'F') | (unsigned long long)bytes_equal(w[1], 'F') << 32;
+    unsigned long long f1 = bytes_equal(w[2], 'F') | (unsigned long long)bytes_equal(w[3], 'F') << 32;
+    while (f0 | f1) {
+      uint32_t k;
+      if (f0) {
+        k = (uint32_t)(__ffsll((long long)f0) - 1) >> 3;
+        f0 &= f0 - 1;
+      } else {
+        k = 8 + ((uint32_t)(__ffsll((long long)f1) - 1) >> 3);
+        f1 &= f1 - 1;
+      }
+      const uint64_t p = p0 + k;
+      uint64_t size;
+      if (p < n && sfwp::block_message(data + p, n - p, &size)) mask |= 1u << k;
+    }
+  }
+  // lanes 4j .. 4j + 3 hold positions [64 (g / 4), + 64)
+  unsigned long long m = mask;
+  m |= (unsigned long long)__shfl_down(mask, 1) << 16;
+  m |= (unsigned long long)__shfl_down(mask, 2) << 32;
+  m |= (unsigned long long)__shfl_down(mask, 3) << 48;
+  if ((threadIdx.x & 3) == 0 && p0 < n) {
+    words[g >> 2] = m;
+    counts[g >> 2] = (uint32_t)__popcll(m);
+  }
+}
+
+// The length (34..48) and size of the message at candidate position p: the
+// tag and the digest's newline were checked when p became a candidate.
+__device__ __forceinline__ uint32_t message_len(const uint8_t* __restrict__ data, uint64_t n, uint64_t p,
+                                                uint64_t* size) {
+  return sfwp::kSizeAt + sfwp::size_field(data + p + sfwp::kSizeAt, n - p - sfwp::kSizeAt, size);
+}
+
+// The 64 bitmap bits from position q on (bits past the bitmap are 0).
+__device__ __forceinline__ unsigned long long bits_from(const unsigned long long* __restrict__ words, uint64_t nw,
+                                                        uint64_t q) {
+  const uint64_t w = q >> 6;
+  const uint32_t s = (uint32_t)(q & 63);
+  unsigned long long v = w < nw ? words[w] >> s : 0ull;
+  if (s && w + 1 < nw) v |= words[w + 1] << (64 - s);
+  return v;
+}
+
+__global__ void __launch_bounds__(256) recv_chain_kernel(const uint8_t* __restrict__ data, uint64_t n,
+                                                         const unsigned long long* __restrict__ words,
+                                                         const uint64_t* __restrict__ ends, uint64_t nw,
+                                                         Result* __restrict__ res) {
+  const uint64_t w = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (w >= nw) return;
+  unsigned long long m = words[w];
+  if (w == 0 && !(m & 1ull)) atomicMin(&res->first_bad, 1ull);  // nothing at byte 0: no message
+  uint64_t i = ends[w] - (uint64_t)__popcll(m);
+  for (; m; m &= m - 1, i++) {
+    const uint64_t p = (w << 6) + (uint64_t)(__ffsll((long long)m) - 1);
+    uint64_t size;
+    const uint32_t L = message_len(data, n, p, &size);
+    const unsigned long long v = bits_from(words, nw, p + 1);        // positions p + 1 ...
+    const bool inside = (v & ((1ull << (L - 1)) - 1)) != 0;          // ... to p + L - 1
+    const bool next = (v >> (L - 1)) & 1ull;                         // p + L
+    if (inside || !next) atomicMin(&res->first_bad, ((unsigned long long)(i + 1) << 1) | (inside ? 0ull : 1ull));
+  }
+}
+
+__global__ void __launch_bounds__(256) recv_extract_kernel(const uint8_t* __restrict__ data, uint64_t n,
+                                                           const unsigned long long* __restrict__ words,
+                                                           const uint64_t* __restrict__ ends, uint64_t nw,
+                                                           uint32_t* __restrict__ digests, uint32_t* __restrict__ sizes,
+                                                           uint64_t cap, Result* __restrict__ res) {
+  const uint64_t w = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (w >= nw) return;
+  const uint64_t k = res->first_bad >> 1;  // the messages (written by the chain kernel, a launch earlier)
+  if (w == 0) {
+    res->cand = ends[nw - 1];
+    res->msgs = k;
+  }
+  unsigned long long m = words[w];
+  uint64_t i = ends[w] - (uint64_t)__popcll(m);
+  for (; m && i < k; m &= m - 1, i++) {
+    const uint64_t p = (w << 6) + (uint64_t)(__ffsll((long long)m) - 1);
+    uint64_t size;
+    const uint32_t L = message_len(data, n, p, &size);
+    if (i == k - 1) res->end = p + L;
+    if (size > 0xFFFFFFFFull) atomicOr(&res->too_large, 1u);
+    if (i >= cap) continue;
+    const uint8_t* d = data + p + sfwp::kTag;  // no alignment: bytes, stored as the table's dwords
+    uint32_t* o = digests + 5 * i;
+#pragma unroll
+    for (int j = 0; j < 5; j++)
+      o[j] = (uint32_t)d[4 * j] | (uint32_t)d[4 * j + 1] << 8 | (uint32_t)d[4 * j + 2] << 16 |
+             (uint32_t)d[4 * j + 3] << 24;
+    sizes[i] = (uint32_t)size;
+  }
+}
+
+struct Widen {
+  __host__ __device__ uint64_t operator()(uint32_t v) const { return (uint64_t)v; }
+};
+
+std::atomic<uint64_t> g_parse_stats[4];  // sf_test_wire_parse_stats
+
+inline void reset_stats() {
+  for (auto& v : g_parse_stats) v.store(0, std::memory_order_relaxed);
+}
+
+inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+}  // namespace
+
+using namespace sfi;
+
+namespace {
+
+// Stream-ordered scratch that goes back on every path out of a call.
+struct Scratch {
+  void* p = nullptr;
+  hipStream_t s;
+  explicit Scratch(hipStream_t s_) : s(s_) {}
+  ~Scratch() { stream_free(p, s); }
+};
+
+struct Parsed {
+  uint64_t count = 0, consumed = 0;
+  int stop = sfwp::kEnd;
+};
+
+// The serial parse on the host and the upload of its first min(count, cap)
+// entries.  h_wire: the run in host memory if the caller has it there, else
+// it is copied back from d_wire through a pinned stage.
+int parse_on_host(const uint8_t* d_wire, const uint8_t* h_wire, uint64_t n, uint8_t* d_digests, uint32_t* d_sizes,
+                  uint64_t cap, Parsed* out, hipStream_t s, HostLease* lease) {
+  std::unique_ptr<HostLease> own;
+  if (!lease) {
+    own.reset(new HostLease);
+    lease = own.get();
+  }
+  const uint64_t most = n / sfwp::kMinMessage + 1;
+  StageBufs sb;
+  int rc = stage_bufs(*lease, 1, h_wire ? kNoBuf : n, kNoBuf, kNoBuf, &sb);
+  void *pdig = nullptr, *psz = nullptr;
+  if (rc == SF_OK) rc = lease->pin(kSlotDigests + 1, most * 20, &pdig);
+  if (rc == SF_OK) rc = lease->pin(kSlotAux + 1, most * 4, &psz);
+  if (rc != SF_OK) return rc;
+  if (!h_wire) {
+    SF_HIP(hipMemcpyAsync(sb.pin, d_wire, n, hipMemcpyDeviceToHost, s));
+    SF_HIP(hipStreamSynchronize(s));
+    h_wire = static_cast<const uint8_t*>(sb.pin);
+  }
+  bool too_large = false;
+  sfwp::parse_run(h_wire, n, static_cast<uint8_t*>(pdig), static_cast<uint32_t*>(psz), most, &out->count,
+                  &out->consumed, &out->stop, &too_large);
+  g_parse_stats[1].store(out->count, std::memory_order_relaxed);
+  g_parse_stats[2].store(1, std::memory_order_relaxed);
+  if (too_large) return SF_ERANGE;
+  const uint64_t up = std::min(out->count, cap);
+  if (up) {
+    SF_HIP(hipMemcpyAsync(d_digests, pdig, up * 20, hipMemcpyHostToDevice, s));
+    SF_HIP(hipMemcpyAsync(d_sizes, psz, up * 4, hipMemcpyHostToDevice, s));
+    SF_HIP(hipStreamSynchronize(s));  // the pinned stages go back to the cache
+  }
+  return SF_OK;
+}
+
+// The messages of d_wire[0, n) (n > 0): the first min(count, cap) into
+// d_digests / d_sizes, the count, the bytes and the stop into *out.  Blocking.
+int parse_run_device(const uint8_t* d_wire, const uint8_t* h_wire, uint64_t n, uint8_t* d_digests, uint32_t* d_sizes,
+                     uint64_t cap, Parsed* out, hipStream_t s, HostLease* lease) {
+  if (knob(K_TEST_WIRE_PARSE_HOST) == 1) return parse_on_host(d_wire, h_wire, n, d_digests, d_sizes, cap, out, s, lease);
+  const uint64_t nw = ceil_div(n, 64);
+  size_t tmp = 0;
+  {
+    uint32_t* in = nullptr;
+    uint64_t* o = nullptr;
+    if (rocprim::inclusive_scan(nullptr, tmp, in, o, (size_t)nw, rocprim::plus<uint64_t>(), s) != hipSuccess) {
+      (void)hipGetLastError();
+      return SF_ENODEV;
+    }
+  }
+  const size_t wb = align256(nw * 8), cb = align256(nw * 4);
+  Scratch ws(s);
+  int rc = stream_alloc(&ws.p, 256 + 2 * wb + cb + tmp + 8, s);
+  if (rc != SF_OK) return rc;
+  uint8_t* base = static_cast<uint8_t*>(ws.p);
+  Result* res = reinterpret_cast<Result*>(base);
+  unsigned long long* words = reinterpret_cast<unsigned long long*>(base + 256);
+  uint64_t* ends = reinterpret_cast<uint64_t*>(base + 256 + wb);
+  uint32_t* counts = reinterpret_cast<uint32_t*>(base + 256 + 2 * wb);
+  void* scan_tmp = base + 256 + 2 * wb + cb;
+  SF_HIP(hipMemsetAsync(res, 0, sizeof(Result), s));
+  SF_HIP(hipMemsetAsync(&res->first_bad, 0xFF, sizeof(res->first_bad), s));
+  clear_stale_error();
+  hipLaunchKernelGGL(recv_candidates_kernel, dim3((unsigned)ceil_div(n, 256 * kPerLane)), dim3(256), 0, s, d_wire, n,
+                     words, counts);
+  SF_HIP(hipGetLastError());
+  if (rocprim::inclusive_scan(scan_tmp, tmp, counts, ends, (size_t)nw, rocprim::plus<uint64_t>(), s) != hipSuccess) {
+    (void)hipGetLastError();
+    return SF_ENODEV;
+  }
+  const dim3 gw((unsigned)ceil_div(nw, 256));
+  clear_stale_error();
+  hipLaunchKernelGGL(recv_chain_kernel, gw, dim3(256), 0, s, d_wire, n, words, ends, nw, res);
+  SF_HIP(hipGetLastError());
+  clear_stale_error();
+  hipLaunchKernelGGL(recv_extract_kernel, gw, dim3(256), 0, s, d_wire, n, words, ends, nw,
+                     reinterpret_cast<uint32_t*>(d_digests), d_sizes, cap, res);
+  SF_HIP(hipGetLastError());
+  Result h{};
+  SF_HIP(hipMemcpyAsync(&h, res, sizeof(Result), hipMemcpyDeviceToHost, s));
+  SF_HIP(hipStreamSynchronize(s));
+  g_parse_stats[0].store(h.cand, std::memory_order_relaxed);
+  if (h.msgs && !(h.first_bad & 1ull))  // a candidate inside the last chained message
+    return parse_on_host(d_wire, h_wire, n, d_digests, d_sizes, cap, out, s, lease);
+  g_parse_stats[1].store(h.msgs, std::memory_order_relaxed);
+  if (h.too_large) return SF_ERANGE;
+  out->count = h.msgs;
+  out->consumed = h.end;
+  // what stands at E: at most one message's bytes decide it
+  uint8_t tail[sfwp::kMaxMessage];
+  const uint64_t tn = std::min<uint64_t>(n - h.end, sizeof(tail));
+  if (tn) {
+    if (h_wire) {
+      memcpy(tail, h_wire + h.end, tn);
+    } else {
+      SF_HIP(hipMemcpyAsync(tail, d_wire + h.end, tn, hipMemcpyDeviceToHost, s));
+      SF_HIP(hipStreamSynchronize(s));
+    }
+  }
+  uint32_t len;
+  uint64_t size;
+  // (a whole message cannot stand at E: E would be a candidate and chained)
+  const int c = sfwp::classify(tail, tn, &len, &size);
+  out->stop = c == sfwp::kBlock ? sfwp::kMalformed : c;
+  return SF_OK;
+}
+
+int parse_blocks_device(const void* d_wire, uint64_t n_bytes, void* d_digests, uint32_t* d_sizes, uint64_t cap,
+                        uint64_t* n_out, uint64_t* consumed, int* stop, hipStream_t s) {
+  reset_stats();
+  if (n_out) *n_out = 0;
+  if (consumed) *consumed = 0;
+  if (stop) *stop = SF_WIRE_END;
+  if (!n_out || !consumed || !stop || (n_bytes && !d_wire) || n_bytes > kMaxRun ||
+      (reinterpret_cast<uintptr_t>(d_digests) & 3u))
+    return SF_EINVAL;
+  if (n_bytes == 0) return SF_OK;
+  if (!d_digests || !d_sizes) cap = 0;
+  Parsed p;
+  const int rc = parse_run_device(static_cast<const uint8_t*>(d_wire), nullptr, n_bytes,
+                                  static_cast<uint8_t*>(d_digests), d_sizes, cap, &p, s, nullptr);
+  if (rc != SF_OK) return rc;
+  *n_out = p.count;
+  *consumed = p.consumed;
+  *stop = p.stop;
+  return p.count > cap ? SF_ENOSPC : SF_OK;
+}
+
+struct ReceiveArgs {
+  const sf_block_set* set;
+  uint64_t base_offset;
+  void* d_digests;
+  uint32_t* d_sizes;
+  uint64_t* d_offsets;
+  int64_t* d_rows;
+  uint64_t cap;
+  uint64_t *n_out, *consumed;
+  int* stop;
+  uint64_t* end_offset;
+};
+
+int check_receive_args(const ReceiveArgs& a, const void* wire, uint64_t n_bytes) {
+  reset_stats();
+  if (a.n_out) *a.n_out = 0;
+  if (a.consumed) *a.consumed = 0;
+  if (a.stop) *a.stop = SF_WIRE_END;
+  if (a.end_offset) *a.end_offset = a.base_offset;
+  if (!a.n_out || !a.consumed || !a.stop || !a.end_offset || (n_bytes && !wire) || n_bytes > kMaxRun)
+    return SF_EINVAL;
+  return SF_OK;
+}
+
+// Parse, then the running offsets, then the lookup, on s.  Blocking.
+int receive_device(const ReceiveArgs& a, const uint8_t* d_wire, const uint8_t* h_wire, uint64_t n_bytes,
+                   hipStream_t s, HostLease* lease) {
+  uint64_t cap = a.cap;
+  if (!a.d_digests || !a.d_sizes || !a.d_offsets || (a.set && !a.d_rows)) cap = 0;  // a query
+  Parsed p;
+  int rc = parse_run_device(d_wire, h_wire, n_bytes, static_cast<uint8_t*>(a.d_digests), a.d_sizes, cap, &p, s, lease);
+  if (rc != SF_OK) return rc;
+  *a.n_out = p.count;
+  *a.consumed = p.consumed;
+  *a.stop = p.stop;
+  if (p.count > cap) return SF_ENOSPC;
+  if (p.count == 0) return SF_OK;
+  // d_offsets[i] = base_offset + sizes[0] + ... + sizes[i - 1], in 64 bits
+  auto in = rocprim::make_transform_iterator(a.d_sizes, Widen());
+  size_t tmp = 0;
+  if (rocprim::exclusive_scan(nullptr, tmp, in, a.d_offsets, (uint64_t)a.base_offset, (size_t)p.count,
+                              rocprim::plus<uint64_t>(), s) != hipSuccess) {
+    (void)hipGetLastError();
+    return SF_ENODEV;
+  }
+  Scratch ws(s);
+  if ((rc = stream_alloc(&ws.p, tmp + 8, s)) != SF_OK) return rc;
+  if (rocprim::exclusive_scan(ws.p, tmp, in, a.d_offsets, (uint64_t)a.base_offset, (size_t)p.count,
+                              rocprim::plus<uint64_t>(), s) != hipSuccess) {
+    (void)hipGetLastError();
+    return SF_ENODEV;
+  }
+  if (a.set && (rc = sf_block_set_lookup(a.set, a.d_digests, p.count, a.d_rows, s)) != SF_OK) return rc;
+  uint64_t last_off = 0;
+  uint32_t last_size = 0;
+  SF_HIP(hipMemcpyAsync(&last_off, a.d_offsets + p.count - 1, 8, hipMemcpyDeviceToHost, s));
+  SF_HIP(hipMemcpyAsync(&last_size, a.d_sizes + p.count - 1, 4, hipMemcpyDeviceToHost, s));
+  SF_HIP(hipStreamSynchronize(s));
+  *a.end_offset = last_off + last_size;
+  return SF_OK;
+}
+
+constexpr uint64_t kUploadPiece = 64ull << 20;  // bytes of the run per pinned stage
+
+int receive_buffer(const sf_block_set* set, const uint8_t* wire, uint64_t n_bytes, uint64_t base_offset,
+                   sf_block_sig* out, int64_t* src_rows, uint64_t cap, uint64_t* n_out, uint64_t* consumed,
+                   int* stop, uint64_t* end_offset) {
+  ReceiveArgs a{set, base_offset, nullptr, nullptr, nullptr, nullptr, 0, n_out, consumed, stop, end_offset};
+  int rc = check_receive_args(a, wire, n_bytes);
+  if (rc != SF_OK || n_bytes == 0) return rc;
+  if (!out || (set && !src_rows)) cap = 0;
+  HostLease res;
+  hipStream_t* st;
+  hipEvent_t* ev;
+  if ((rc = res.streams(st, ev)) != SF_OK) return rc;
+  hipStream_t s = st[0];
+  // the run to HBM through the two pinned stages
+  void* d_wire = nullptr;
+  if ((rc = res.dev(kSlotFileTable, n_bytes, &d_wire)) != SF_OK) return rc;
+  const uint64_t piece = std::min(n_bytes, kUploadPiece);
+  void* pin[2] = {nullptr, nullptr};
+  for (int b = 0; b < 2; b++)
+    if ((rc = res.pin(kSlotData + b, piece, &pin[b])) != SF_OK) return rc;
+  rc = two_stage(
+      ceil_div(n_bytes, piece),
+      [&](uint64_t k, int b) {
+        const uint64_t o = k * piece, m = std::min(piece, n_bytes - o);
+        memcpy(pin[b], wire + o, m);
+        SF_HIP(hipMemcpyAsync(static_cast<uint8_t*>(d_wire) + o, pin[b], m, hipMemcpyHostToDevice, s));
+        SF_HIP(hipEventRecord(ev[b], s));
+        return SF_OK;
+      },
+      [&](uint64_t, int b) {
+        SF_HIP(hipEventSynchronize(ev[b]));
+        return SF_OK;
+      });
+  if (rc != SF_OK) return rc;
+  // device rows for every message the run can hold: offsets, rows, sizes
+  const uint64_t most = n_bytes / sfwp::kMinMessage + 1;
+  void *ddig = nullptr, *daux = nullptr;
+  if ((rc = res.dev(kSlotDigests, most * 20, &ddig)) != SF_OK) return rc;
+  if ((rc = res.dev(kSlotAux, most * 20, &daux)) != SF_OK) return rc;
+  a.d_digests = ddig;
+  a.d_offsets = static_cast<uint64_t*>(daux);
+  a.d_rows = reinterpret_cast<int64_t*>(a.d_offsets + most);
+  a.d_sizes = reinterpret_cast<uint32_t*>(a.d_rows + most);
+  a.cap = most;
+  if ((rc = receive_device(a, static_cast<const uint8_t*>(d_wire), wire, n_bytes, s, &res)) != SF_OK) return rc;
+  const uint64_t n = *n_out;
+  if (n > cap) return SF_ENOSPC;
+  if (n == 0) return SF_OK;
+  void *pdig = nullptr, *paux = nullptr;
+  if ((rc = res.pin(kSlotDigests, n * 20, &pdig)) != SF_OK) return rc;
+  if ((rc = res.pin(kSlotAux, most * 20, &paux)) != SF_OK) return rc;
+  SF_HIP(hipMemcpyAsync(pdig, ddig, n * 20, hipMemcpyDeviceToHost, s));
+  SF_HIP(hipMemcpyAsync(paux, daux, (2 * most + n) * 8 - n * 4, hipMemcpyDeviceToHost, s));
+  SF_HIP(hipStreamSynchronize(s));
+  const uint64_t* po = static_cast<const uint64_t*>(paux);
+  const int64_t* pr = reinterpret_cast<const int64_t*>(po + most);
+  const uint32_t* pz = reinterpret_cast<const uint32_t*>(pr + most);
+  for (uint64_t i = 0; i < n; i++) {
+    out[i].offset = po[i];
+    out[i].size = pz[i];
+    memcpy(out[i].sha1, static_cast<const uint8_t*>(pdig) + 20 * i, 20);
+    if (src_rows) src_rows[i] = set ? pr[i] : -1;
+  }
+  return SF_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sf_wire_parse_blocks_device(const void* d_wire, uint64_t n_bytes, void* d_digests, uint32_t* d_sizes,
+                                uint64_t cap, uint64_t* n_out, uint64_t* consumed, int* stop, void* stream) {
+  return guarded(
+      [&] { return parse_blocks_device(d_wire, n_bytes, d_digests, d_sizes, cap, n_out, consumed, stop, as_stream(stream)); });
+}
+
+int sf_receive_blocks_device(const sf_block_set* set, const void* d_wire, uint64_t n_bytes, uint64_t base_offset,
+                             void* d_digests, uint32_t* d_sizes, uint64_t* d_offsets, int64_t* d_rows, uint64_t cap,
+                             uint64_t* n_out, uint64_t* consumed, int* stop, uint64_t* end_offset, void* stream) {
+  return guarded([&]() -> int {
+    const ReceiveArgs a{set, base_offset, d_digests, d_sizes, d_offsets, d_rows, cap, n_out, consumed, stop, end_offset};
+    const int rc = check_receive_args(a, d_wire, n_bytes);
+    if (rc != SF_OK || n_bytes == 0) return rc;
+    if (reinterpret_cast<uintptr_t>(d_digests) & 3u) return SF_EINVAL;
+    return receive_device(a, static_cast<const uint8_t*>(d_wire), nullptr, n_bytes, as_stream(stream), nullptr);
+  });
+}
+
+int sf_receive_blocks_buffer(const sf_block_set* set, const void* wire, uint64_t n_bytes, uint64_t base_offset,
+                             sf_block_sig* out, int64_t* src_rows, uint64_t cap, uint64_t* n_out, uint64_t* consumed,
+                             int* stop, uint64_t* end_offset) {
+  return guarded([&] {
+    return receive_buffer(set, static_cast<const uint8_t*>(wire), n_bytes, base_offset, out, src_rows, cap, n_out,
+                          consumed, stop, end_offset);
+  });
+}
+
+int sf_test_wire_parse_stats(uint64_t out[4]) {
+  if (!out) return SF_EINVAL;
+  for (int k = 0; k < 4; k++) out[k] = g_parse_stats[k].load(std::memory_order_relaxed);
+  return SF_OK;
+}
+
+}  // extern "C"

@@ -472,6 +472,42 @@ class BlockSet:
                                                 _stream_ptr(self.table, self.stream)), "sf_block_set_lookup")
         return rows
 
+    def receive(self, run: torch.Tensor, base_offset: int = 0):
+        """A FILE_BLOCK run as the destination receives it, in one call
+        (sf_receive_blocks_device): the messages at the start of ``run`` (a
+        uint8 HBM tensor) are parsed on the device, each gets its offset in
+        the incoming file (``base_offset`` + the sizes before it, the running
+        offset of src/sync/fs.rs:477) and its lookup in this set.  Returns
+        (digests uint8[n, 20], sizes uint32[n], offsets int64[n], rows
+        int64[n], consumed, stop, end_offset): ``rows`` as ``lookup`` gives
+        them, ``consumed`` / ``stop`` as wire.parse_blocks_device, and
+        ``end_offset`` the offset after the last message -- the file's size
+        when the run stops at FILE_END, or the next call's ``base_offset``
+        when it arrives in pieces.  Blocking."""
+        _require_device(run, "run", torch.uint8, self.table.device)
+        if run.dim() != 1:
+            raise ValueError("run must be a flat uint8 tensor")
+        if not self._h:
+            raise ValueError("BlockSet is closed")
+        nb = run.numel()
+        cap = nb // 34 + 1  # a message is at least 34 bytes
+        n, consumed, end = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+        stop = ctypes.c_int(0)
+        dev = self.table.device
+        with _on(dev, self.stream):
+            digests = torch.empty((cap, 20), dtype=torch.uint8, device=dev)
+            sizes = torch.empty(cap, dtype=torch.int32, device=dev)
+            offsets = torch.empty(cap, dtype=torch.int64, device=dev)
+            rows = torch.empty(cap, dtype=torch.int64, device=dev)
+            check(lib().sf_receive_blocks_device(self._h, run.data_ptr() if nb else None, nb, int(base_offset),
+                                                 digests.data_ptr(), sizes.data_ptr(), offsets.data_ptr(),
+                                                 rows.data_ptr(), cap, ctypes.byref(n), ctypes.byref(consumed),
+                                                 ctypes.byref(stop), ctypes.byref(end),
+                                                 _stream_ptr(self.table, self.stream)), "sf_receive_blocks_device")
+        k = n.value
+        return (digests[:k], sizes[:k].view(torch.uint32), offsets[:k], rows[:k], consumed.value, stop.value,
+                end.value)
+
     def close(self) -> None:
         if self._h:
             with _on(self.table.device, self.stream):

@@ -386,6 +386,17 @@ class Index:
             "WHERE blocks.hash = ? AND blocks.present = 1;", (hash.to_sql(),)).fetchone()
         return (PurePath(row[0]), int(row[1]), int(row[2])) if row else None
 
+    def _lookup_table(self):
+        """What a device BlockSet of this index is built from: every block row
+        in rowid order as (hash, get_block would take it, file name, offset,
+        size), their digests as uint8[n, 20] and those flags."""
+        rows = self.db.execute(
+            "SELECT blocks.hash, blocks.present = 1 AND files.file_id IS NOT NULL, files.name, blocks.offset, "
+            "blocks.size FROM blocks LEFT JOIN files ON blocks.file_id = files.file_id "
+            "ORDER BY blocks.rowid;").fetchall()
+        table = np.frombuffer(bytes.fromhex("".join(r[0] for r in rows)), np.uint8).reshape(-1, 20)
+        return rows, table, np.fromiter((bool(r[1]) for r in rows), bool, len(rows))
+
     def get_blocks(self, hashes: Sequence[HashDigest], device=None) -> List[Optional[Tuple[PurePath, int, int]]]:
         """get_block for a whole list of hashes -- a FILE_BLOCK run as the
         destination receives it (src/sync/fs.rs:461-476) -- answered by one
@@ -396,20 +407,57 @@ class Index:
         import torch
 
         from .device import BlockSet
-        rows = self.db.execute(
-            "SELECT blocks.hash, blocks.present = 1 AND files.file_id IS NOT NULL, files.name, blocks.offset, "
-            "blocks.size FROM blocks LEFT JOIN files ON blocks.file_id = files.file_id "
-            "ORDER BY blocks.rowid;").fetchall()
+        rows, table, present = self._lookup_table()
         if not hashes:
             return []
         dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        table = np.frombuffer(bytes.fromhex("".join(r[0] for r in rows)), np.uint8).reshape(-1, 20)
-        present = np.fromiter((bool(r[1]) for r in rows), bool, len(rows))
         q = np.frombuffer(b"".join(h.bytes for h in hashes), np.uint8).reshape(-1, 20)
         t = torch.from_numpy(table.copy()).to(dev)
         with BlockSet(t, torch.from_numpy(present).to(dev)) as bset:
             found = bset.lookup(torch.from_numpy(q.copy()).to(dev)).cpu().numpy()
         return [None if r < 0 else (PurePath(rows[r][2]), int(rows[r][3]), int(rows[r][4])) for r in found]
+
+    def receive_file_blocks(self, file_id: int, data, device=None) -> List[Tuple[PurePath, int, int, int]]:
+        """The sink's GetFiles state for one incoming file
+        (src/sync/fs.rs:461-498) in one device call.  ``data``: the bytes
+        after the file's FILE_START up to and including FILE_END -- its
+        FILE_BLOCK run.  The run is parsed, offset and looked up against this
+        index's blocks (the table of ``get_blocks``) by one
+        ``BlockSet.receive``; every message becomes a row of ``file_id`` in
+        one executemany -- present = 1 where get_block finds the block
+        (add_block), present = 0 where it does not (add_missing_block) -- and
+        the file's size and blocks_hash are set from the run's end offset.
+
+        Returns the copy list [(from_name, from_offset, to_offset, size)]: the
+        blocks recorded as present are NOT written by this call (file I/O
+        stays out of Index).  The caller copies each of them into the file
+        before ``commit()``, as the reference copies each block before its
+        add_block.  A run that does not end with FILE_END right after its
+        last FILE_BLOCK raises wire.ProtocolError, and nothing is written."""
+        import torch
+
+        from . import wire
+        from .device import BlockSet
+        data = bytes(data)
+        rows, table, present = self._lookup_table()
+        dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        run = torch.frombuffer(bytearray(data), dtype=torch.uint8).to(dev) if data else \
+            torch.empty(0, dtype=torch.uint8, device=dev)
+        with BlockSet(torch.from_numpy(table.copy()).to(dev), torch.from_numpy(present).to(dev)) as bset:
+            digests, sizes, offsets, found, consumed, stop, end_offset = bset.receive(run)
+            digests, sizes = digests.cpu().numpy(), sizes.cpu().numpy()
+            offsets, found = offsets.cpu().numpy(), found.cpu().numpy()
+        if stop == wire.SF_WIRE_MALFORMED:
+            raise wire.ProtocolError("Malformed FILE_BLOCK run at byte %d" % consumed)
+        if stop != wire.SF_WIRE_OTHER or data[consumed:] != b"FILE_END\n":
+            raise wire.ProtocolError("FILE_BLOCK run does not end with FILE_END (byte %d)" % consumed)
+        self.begin()
+        self.db.executemany(
+            "INSERT INTO blocks(hash, file_id, offset, size, present) VALUES(?, ?, ?, ?, ?);",
+            ((bytes(d).hex(), file_id, int(o), int(s), int(r >= 0)) for d, o, s, r in zip(digests, offsets, sizes, found)))
+        self.set_file_size_and_compute_blocks_hash(file_id, end_offset)
+        return [(PurePath(rows[r][2]), int(rows[r][3]), int(o), int(s))
+                for o, s, r in zip(offsets, sizes, found) if r >= 0]
 
     def get_file(self, name) -> Optional[Tuple[int, DateTimeUtc, Optional[HashDigest]]]:
         row = self.db.execute(

@@ -14,7 +14,7 @@ import ctypes
 import re
 from typing import List, Optional, Tuple
 
-from ._lib import check, lib
+from ._lib import SF_WIRE_END, SF_WIRE_INCOMPLETE, SF_WIRE_MALFORMED, SF_WIRE_OTHER, check, lib  # noqa: F401
 from .digest import HashDigest
 
 
@@ -198,6 +198,43 @@ def blocks_device(digests, sizes, stream=None):
             check(lib().sf_wire_blocks_device(digests.data_ptr(), sizes.data_ptr(), n, out.data_ptr(), out.numel(),
                                               ctypes.byref(need), s), "sf_wire_blocks_device")
     return out
+
+
+def parse_blocks_device(run, stream=None):
+    """The inverse of ``blocks_device``: the FILE_BLOCK messages at the start
+    of ``run``, a uint8 HBM tensor, parsed on the device
+    (sf_wire_parse_blocks_device) -> (digests uint8[n, 20], sizes uint32[n],
+    consumed, stop).  The n messages are exactly those ``Parser`` reads from
+    byte 0 until something else stands there; ``consumed`` is their bytes and
+    ``stop`` says what stands at ``run[consumed:]``: SF_WIRE_END (nothing),
+    SF_WIRE_INCOMPLETE (the start of a message), SF_WIRE_OTHER (another
+    command's complete line: FILE_END, FILE_START, ...) or SF_WIRE_MALFORMED
+    (``Parser`` would raise there).  A size above 2^32 - 1 raises SfError
+    (SF_ERANGE).  Blocking."""
+    from .device import _on, _require_device
+    import torch
+    _require_device(run, "run", torch.uint8)
+    if run.dim() != 1:
+        raise ValueError("run must be a flat uint8 tensor")
+    nb = run.numel()
+    cap = nb // 34 + 1  # a message is at least 34 bytes
+    n, consumed, stop = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_int(0)
+    with _on(run.device, stream):
+        digests = torch.empty((cap, 20), dtype=torch.uint8, device=run.device)
+        sizes = torch.empty(cap, dtype=torch.int32, device=run.device)
+        s = torch.cuda.current_stream(run.device).cuda_stream
+        check(lib().sf_wire_parse_blocks_device(run.data_ptr() if nb else None, nb, digests.data_ptr(),
+                                                sizes.data_ptr(), cap, ctypes.byref(n), ctypes.byref(consumed),
+                                                ctypes.byref(stop), s), "sf_wire_parse_blocks_device")
+    return digests[:n.value], sizes[:n.value].view(torch.uint32), consumed.value, stop.value
+
+
+def parse_stats():
+    """Test hook (sf_test_wire_parse_stats): (candidates, messages, whether the
+    host fallback ran, 0) of this process's last FILE_BLOCK parse."""
+    out = (ctypes.c_uint64 * 4)()
+    check(lib().sf_test_wire_parse_stats(out), "sf_test_wire_parse_stats")
+    return tuple(int(v) for v in out)
 
 
 def blocks_to_fd(digests, sizes, fd: int, stream=None) -> int:
