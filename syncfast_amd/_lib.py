@@ -30,27 +30,6 @@ SF_WIRE_END, SF_WIRE_INCOMPLETE, SF_WIRE_OTHER, SF_WIRE_MALFORMED = 0, 1, 2, 3
 HASH_DIGEST_LEN = 20
 MAX_BLOCK_SIZE = 32 << 20
 
-# Every symbol include/syncfast_amd.h declares (checked by the CPU tests).
-EXPORTED = (
-    "sf_version", "sf_strerror", "sf_device_count", "sf_set_device", "sf_release_host_cache",
-    "sf_index_device_fixed", "sf_index_device_blocks", "sf_index_device_batch",
-    "sf_index_device_fixed_weak", "sf_index_device_blocks_weak", "sf_index_device_batch_chained",
-    "sf_index_device_batch_chained_cols",
-    "sf_fill_splitmix_device", "sf_wire_file_blocks_device", "sf_wire_blocks_device", "sf_wire_blocks_fd", "sf_wire_file_blocks_fd", "sf_index_buffer", "sf_index_buffer_blocks", "sf_index_file_blocks", "sf_file_stamp_fd", "sf_index_fd_blocks", "sf_index_fd_fixed", "sf_index_file", "sf_index_file_range", "sf_index_fd", "sf_free_rows", "sf_index_files",
-    "sf_index_fds_blocks", "sf_cut_fd", "sf_free_cuts", "sf_index_fd_cut", "sf_shard_range", "sf_index_file_multi",
-    "sf_index_device_multi", "sf_index_device_multi_ex",
-    "sf_blocks_hash", "sf_blocks_hash_sigs", "sf_sha1_host",
-    "sf_block_set_build", "sf_block_set_lookup", "sf_block_set_free",
-    "sf_zpaq_cut_buffer", "sf_zpaq_chunker_ops", "sf_cut_device_zpaq", "sf_index_device_zpaq", "sf_index_fd_zpaq",
-    "sf_wire_parse_blocks_device", "sf_receive_blocks_device", "sf_receive_blocks_buffer",
-)
-# Test hooks (include/syncfast_amd_test.h): knobs latched at load, route counters,
-# the explicit-list processing order.
-EXPORTED_TEST = ("sf_test_set_knob", "sf_test_get_knob", "sf_test_get_stat", "sf_test_table_order",
-                 "sf_test_table_order_bits",
-                 "sf_test_set_read_hook", "sf_test_xcd_litmus", "sf_test_multi_plan", "sf_test_zpaq_device_stats",
-                 "sf_test_wire_parse_stats")
-
 
 class SfError(OSError):
     """A negative SF_E* return code (maps to the reference's Error::Io)."""
@@ -95,85 +74,106 @@ class FileDesc(ctypes.Structure):
     _fields_ = [("offset", ctypes.c_uint64), ("len", ctypes.c_uint64)]
 
 
+class ChunkerOps(ctypes.Structure):
+    """sf_chunker_ops (include/syncfast_amd.h): a caller's native chunker."""
+    _fields_ = [("create", ctypes.CFUNCTYPE(ctypes.c_void_p, ctypes.c_void_p)),
+                ("next", ctypes.CFUNCTYPE(ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t)),
+                ("destroy", ctypes.CFUNCTYPE(None, ctypes.c_void_p)),
+                ("ctx", ctypes.c_void_p)]
+
+
+def num_blocks(length: int, block_size: int) -> int:
+    """ceil(len / B); 0 for an empty input (no empty blocks)."""
+    return (length + block_size - 1) // block_size if length else 0
+
+
+def _table():
+    """name -> (restype, argtypes) of every function the two headers declare;
+    tests/test_binding.py holds it against their prototypes."""
+    vp, u64, u32, i32, i64, cp = (ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int, ctypes.c_int64,
+                                  ctypes.c_char_p)
+    P = ctypes.POINTER
+    pu64, pu32, pint, pi64, sig, stamp = P(u64), P(u32), P(i32), P(i64), P(BlockSig), P(FileStamp)
+    public = {  # include/syncfast_amd.h
+        "sf_version": (cp, []),
+        "sf_strerror": (cp, [i32]),
+        "sf_device_count": (i32, [pint]),
+        "sf_set_device": (i32, [i32]),
+        "sf_release_host_cache": (i32, []),
+        "sf_index_device_fixed": (i32, [vp, u64, u32, vp, u64, pu64, vp]),
+        "sf_index_device_blocks": (i32, [vp, u64, vp, vp, u64, vp, vp, vp]),
+        "sf_index_device_fixed_weak": (i32, [vp, u64, u32, vp, vp, u64, pu64, vp]),
+        "sf_index_device_blocks_weak": (i32, [vp, u64, vp, vp, u64, vp, vp, vp, vp]),
+        "sf_index_device_batch": (i32, [vp, u64, P(FileDesc), u32, u32, vp, u64, vp, vp, pu64, vp, vp]),
+        "sf_index_device_batch_chained": (i32, [vp, u32, u64, u32, vp, P(ChainJob), u32, vp]),
+        "sf_index_device_batch_chained_cols": (i32, [vp, u32, u64, u32, u64, u64, vp, P(ChainJob), u32, vp]),
+        "sf_block_set_build": (i32, [vp, vp, u64, P(vp), vp]),
+        "sf_block_set_lookup": (i32, [vp, vp, u64, vp, vp]),
+        "sf_block_set_free": (i32, [vp, vp]),
+        "sf_wire_file_blocks_device": (i32, [vp, u64, u32, u64, vp, u64, pu64, vp]),
+        "sf_wire_blocks_device": (i32, [vp, vp, u64, vp, u64, pu64, vp]),
+        "sf_wire_file_blocks_fd": (i32, [vp, u64, u32, u64, i32, pu64, vp]),
+        "sf_wire_blocks_fd": (i32, [vp, vp, u64, i32, pu64, vp]),
+        "sf_wire_parse_blocks_device": (i32, [vp, u64, vp, vp, u64, pu64, pu64, pint, vp]),
+        "sf_receive_blocks_device": (i32, [vp, vp, u64, u64, vp, vp, vp, vp, u64, pu64, pu64, pint, pu64, vp]),
+        "sf_receive_blocks_buffer": (i32, [vp, vp, u64, u64, sig, vp, u64, pu64, pu64, pint, pu64]),
+        "sf_fill_splitmix_device": (i32, [vp, u64, u64, u64, vp]),
+        "sf_index_buffer": (i32, [vp, u64, u32, sig, u64, pu64]),
+        "sf_index_buffer_blocks": (i32, [vp, u64, vp, vp, u64, sig, vp]),
+        "sf_index_file_blocks": (i32, [cp, vp, vp, u64, sig, vp]),
+        "sf_file_stamp_fd": (i32, [i32, stamp]),
+        "sf_index_fd_blocks": (i32, [i32, stamp, vp, vp, u64, sig, vp]),
+        "sf_index_fd_fixed": (i32, [i32, stamp, u32, sig, u64, pu64, vp]),
+        "sf_index_file": (i32, [cp, u32, sig, u64, pu64, vp]),
+        "sf_index_file_range": (i32, [cp, u64, u64, u32, sig, u64, pu64]),
+        "sf_index_fd": (i32, [i32, u32, P(sig), pu64, vp]),
+        "sf_free_rows": (None, [sig]),
+        "sf_index_files": (i32, [P(cp), u32, u32, u64, sig, u64, pu64, vp, pu64, pu32]),
+        "sf_index_fds_blocks": (i32, [vp, vp, u32, vp, vp, vp, u64, sig, u64, pu64, vp, vp, pu32]),
+        "sf_cut_fd": (i32, [i32, vp, vp, u32, P(vp), P(vp), pu64]),
+        "sf_free_cuts": (None, [vp]),
+        "sf_index_fd_cut": (i32, [i32, vp, vp, u32, P(sig), pu64, vp]),
+        "sf_zpaq_cut_buffer": (i32, [vp, u64, u32, u32, vp, vp, u64, pu64]),
+        "sf_zpaq_chunker_ops": (i32, [u32, u32, vp]),
+        "sf_cut_device_zpaq": (i32, [vp, u64, u32, u32, vp, vp, u64, pu64, vp]),
+        "sf_index_device_zpaq": (i32, [vp, u64, u32, u32, vp, vp, vp, u64, pu64, vp, vp]),
+        "sf_index_fd_zpaq": (i32, [i32, vp, u32, u32, P(sig), pu64, vp]),
+        "sf_shard_range": (i32, [u64, u32, u32, u32, pu64, pu64]),
+        "sf_index_file_multi": (i32, [cp, u32, u32, sig, u64, pu64, vp]),
+        "sf_index_device_multi": (i32, [u32, vp, u64, u32, vp, u32, vp, vp]),
+        "sf_index_device_multi_ex": (i32, [u32, vp, u64, u32, vp, u32, vp, vp, vp]),
+        "sf_blocks_hash": (i32, [vp, u64, vp]),
+        "sf_blocks_hash_sigs": (i32, [sig, u64, vp]),
+        "sf_sha1_host": (i32, [vp, u64, vp]),
+    }
+    # include/syncfast_amd_test.h: knobs latched at load, route counters, the
+    # explicit-list processing order, the read hook, the last call's statistics
+    test = {
+        "sf_test_set_knob": (i32, [cp, i64, pi64]),
+        "sf_test_get_knob": (i32, [cp, pi64]),
+        "sf_test_get_stat": (i32, [cp, pi64]),
+        "sf_test_table_order": (i32, [vp, u64, vp, vp]),
+        "sf_test_table_order_bits": (i32, [vp, u64, u32, vp, vp]),
+        "sf_test_set_read_hook": (i32, [READ_HOOK, vp]),
+        "sf_test_multi_plan": (i32, [u64, u32, u32, u32, i32, vp, vp, vp]),
+        "sf_test_xcd_litmus": (i32, [i32, pu32]),
+        "sf_test_zpaq_device_stats": (i32, [vp]),
+        "sf_test_wire_parse_stats": (i32, [vp]),
+    }
+    return public, test
+
+
+_PUBLIC, _TEST = _table()
+EXPORTED, EXPORTED_TEST = tuple(_PUBLIC), tuple(_TEST)
+
 _lib = None
 
 
 def _declare(L: ctypes.CDLL) -> None:
-    vp, u64, u32, i32 = ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int
-    pu64 = ctypes.POINTER(ctypes.c_uint64)
-    L.sf_version.restype = ctypes.c_char_p
-    L.sf_version.argtypes = []
-    L.sf_strerror.restype = ctypes.c_char_p
-    L.sf_strerror.argtypes = [i32]
-    L.sf_device_count.argtypes = [ctypes.POINTER(ctypes.c_int)]
-    L.sf_set_device.argtypes = [i32]
-    L.sf_release_host_cache.argtypes = []
-    L.sf_index_device_fixed.argtypes = [vp, u64, u32, vp, u64, pu64, vp]
-    L.sf_index_device_blocks.argtypes = [vp, u64, vp, vp, u64, vp, vp, vp]
-    L.sf_index_device_fixed_weak.argtypes = [vp, u64, u32, vp, vp, u64, pu64, vp]
-    L.sf_index_device_blocks_weak.argtypes = [vp, u64, vp, vp, u64, vp, vp, vp, vp]
-    L.sf_index_device_batch_chained.argtypes = [vp, u32, u64, u32, vp, ctypes.POINTER(ChainJob), u32, vp]
-    L.sf_index_device_batch_chained_cols.argtypes = [vp, u32, u64, u32, u64, u64, vp, ctypes.POINTER(ChainJob), u32,
-                                                     vp]
-    L.sf_index_device_batch.argtypes = [vp, u64, ctypes.POINTER(FileDesc), u32, u32, vp, u64, vp, vp, pu64, vp, vp]
-    L.sf_fill_splitmix_device.argtypes = [vp, u64, u64, u64, vp]
-    L.sf_wire_file_blocks_device.argtypes = [vp, u64, u32, u64, vp, u64, pu64, vp]
-    L.sf_wire_blocks_device.argtypes = [vp, vp, u64, vp, u64, pu64, vp]
-    L.sf_wire_blocks_fd.argtypes = [vp, vp, u64, i32, pu64, vp]
-    L.sf_wire_file_blocks_fd.argtypes = [vp, u64, u32, u64, i32, pu64, vp]
-    L.sf_index_buffer.argtypes = [vp, u64, u32, ctypes.POINTER(BlockSig), u64, pu64]
-    L.sf_index_buffer_blocks.argtypes = [vp, u64, vp, vp, u64, ctypes.POINTER(BlockSig), vp]
-    L.sf_index_file_blocks.argtypes = [ctypes.c_char_p, vp, vp, u64, ctypes.POINTER(BlockSig), vp]
-    L.sf_file_stamp_fd.argtypes = [i32, ctypes.POINTER(FileStamp)]
-    L.sf_index_fd_blocks.argtypes = [i32, ctypes.POINTER(FileStamp), vp, vp, u64, ctypes.POINTER(BlockSig), vp]
-    L.sf_index_fd_fixed.argtypes = [i32, ctypes.POINTER(FileStamp), u32, ctypes.POINTER(BlockSig), u64, pu64, vp]
-    L.sf_index_file.argtypes = [ctypes.c_char_p, u32, ctypes.POINTER(BlockSig), u64, pu64, vp]
-    L.sf_index_file_range.argtypes = [ctypes.c_char_p, u64, u64, u32, ctypes.POINTER(BlockSig), u64, pu64]
-    L.sf_index_fd.argtypes = [i32, u32, ctypes.POINTER(ctypes.POINTER(BlockSig)), pu64, vp]
-    L.sf_free_rows.argtypes = [ctypes.POINTER(BlockSig)]
-    L.sf_index_files.argtypes = [ctypes.POINTER(ctypes.c_char_p), u32, u32, u64, ctypes.POINTER(BlockSig), u64,
-                                 pu64, vp, pu64, ctypes.POINTER(ctypes.c_uint32)]
-    L.sf_index_fds_blocks.argtypes = [vp, vp, u32, vp, vp, vp, u64, ctypes.POINTER(BlockSig), u64, pu64, vp, vp,
-                                      ctypes.POINTER(ctypes.c_uint32)]
-    L.sf_cut_fd.argtypes = [i32, vp, vp, u32, ctypes.POINTER(vp), ctypes.POINTER(vp), pu64]
-    L.sf_free_cuts.argtypes = [vp]
-    L.sf_free_cuts.restype = None
-    L.sf_index_fd_cut.argtypes = [i32, vp, vp, u32, ctypes.POINTER(ctypes.POINTER(BlockSig)), pu64, vp]
-    L.sf_shard_range.argtypes = [u64, u32, u32, u32, pu64, pu64]
-    L.sf_index_file_multi.argtypes = [ctypes.c_char_p, u32, u32, ctypes.POINTER(BlockSig), u64, pu64, vp]
-    L.sf_index_device_multi.argtypes = [u32, vp, u64, u32, vp, u32, vp, vp]
-    L.sf_index_device_multi_ex.argtypes = [u32, vp, u64, u32, vp, u32, vp, vp, vp]
-    L.sf_blocks_hash.argtypes = [vp, u64, vp]
-    L.sf_blocks_hash_sigs.argtypes = [ctypes.POINTER(BlockSig), u64, vp]
-    L.sf_sha1_host.argtypes = [vp, u64, vp]
-    L.sf_block_set_build.argtypes = [vp, vp, u64, ctypes.POINTER(vp), vp]
-    L.sf_block_set_lookup.argtypes = [vp, vp, u64, vp, vp]
-    L.sf_block_set_free.argtypes = [vp, vp]
-    L.sf_zpaq_cut_buffer.argtypes = [vp, u64, u32, u32, vp, vp, u64, pu64]
-    L.sf_zpaq_chunker_ops.argtypes = [u32, u32, vp]
-    L.sf_cut_device_zpaq.argtypes = [vp, u64, u32, u32, vp, vp, u64, pu64, vp]
-    L.sf_index_device_zpaq.argtypes = [vp, u64, u32, u32, vp, vp, vp, u64, pu64, vp, vp]
-    L.sf_index_fd_zpaq.argtypes = [i32, vp, u32, u32, ctypes.POINTER(ctypes.POINTER(BlockSig)), pu64, vp]
-    L.sf_test_zpaq_device_stats.argtypes = [vp]
-    pint = ctypes.POINTER(ctypes.c_int)
-    L.sf_wire_parse_blocks_device.argtypes = [vp, u64, vp, vp, u64, pu64, pu64, pint, vp]
-    L.sf_receive_blocks_device.argtypes = [vp, vp, u64, u64, vp, vp, vp, vp, u64, pu64, pu64, pint, pu64, vp]
-    L.sf_receive_blocks_buffer.argtypes = [vp, vp, u64, u64, ctypes.POINTER(BlockSig), vp, u64, pu64, pu64, pint,
-                                           pu64]
-    L.sf_test_wire_parse_stats.argtypes = [vp]
-    pi64 = ctypes.POINTER(ctypes.c_int64)
-    L.sf_test_set_knob.argtypes = [ctypes.c_char_p, ctypes.c_int64, pi64]
-    L.sf_test_get_knob.argtypes = [ctypes.c_char_p, pi64]
-    L.sf_test_get_stat.argtypes = [ctypes.c_char_p, pi64]
-    L.sf_test_table_order.argtypes = [vp, u64, vp, vp]
-    L.sf_test_table_order_bits.argtypes = [vp, u64, ctypes.c_uint32, vp, vp]
-    L.sf_test_set_read_hook.argtypes = [READ_HOOK, vp]
-    L.sf_test_xcd_litmus.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_uint32)]
-    L.sf_test_multi_plan.argtypes = [u64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int, vp, vp, vp]
-    for name in EXPORTED + EXPORTED_TEST:
-        if name not in ("sf_version", "sf_strerror", "sf_free_rows"):
-            getattr(L, name).restype = ctypes.c_int
-    L.sf_free_rows.restype = None
+    for table in (_PUBLIC, _TEST):
+        for name, (restype, argtypes) in table.items():
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, argtypes
 
 
 def lib() -> ctypes.CDLL:
@@ -200,6 +200,24 @@ def _strerror(code: int) -> str:
 def check(rc: int, what: str = "") -> None:
     if rc != SF_OK:
         raise SfError(rc, what)
+
+
+def retry_enospc(call, cap: int, tries: int, what=""):
+    """An entry point whose output is sized by a guess: ``call(cap)`` runs it
+    with room for ``cap`` and returns (rc, need, value).  On SF_ENOSPC with a
+    need above ``cap`` it is called again with that need, ``tries`` calls at
+    the most (a file may grow between two calls; one that grows every time
+    ends as SF_ENOSPC).  Returns the last (need, value); any other code, or
+    the last SF_ENOSPC, raises SfError (``what``: a string, or a function
+    of the failed call's code that gives one)."""
+    for attempt in range(tries):
+        rc, need, value = call(cap)
+        if rc != SF_ENOSPC or need <= cap or attempt == tries - 1:
+            break
+        cap = need
+    if rc != SF_OK:
+        raise SfError(rc, what(rc) if callable(what) else what)
+    return need, value
 
 
 def get_knob(name: str) -> int:
@@ -242,25 +260,30 @@ def set_read_hook(fn) -> None:
     _read_hook_ref = thunk
 
 
+def _elf_sections(b: bytes):
+    """(section header tuples, section names) of an ELF64 image; a header is
+    (name, type, flags, addr, offset, size, link, info, addralign, entsize)."""
+    import struct
+    if b[:4] != b"\x7fELF" or b[4] != 2:
+        raise ValueError("not an ELF64 image")
+    shoff, = struct.unpack_from("<Q", b, 0x28)
+    shentsize, shnum, shstrndx = struct.unpack_from("<HHH", b, 0x3A)
+    secs = [struct.unpack_from("<IIQQQQIIQQ", b, shoff + i * shentsize) for i in range(shnum)]
+    stro = secs[shstrndx][4]
+    return secs, [b[stro + s[0]: b.index(b"\0", stro + s[0])] for s in secs]
+
+
 def _code_objects(path: str):
     """(triple, bytes) of every gfx950 code object in the library's
     .hip_fatbin section (one clang offload bundle per GPU translation unit)."""
     import struct
     with open(path or LIB_PATH, "rb") as f:
         b = f.read()
-    if b[:4] != b"\x7fELF" or b[4] != 2:
-        raise ValueError("not an ELF64 library")
-    shoff, = struct.unpack_from("<Q", b, 0x28)
-    shentsize, shnum, shstrndx = struct.unpack_from("<HHH", b, 0x3A)
-    secs = [struct.unpack_from("<IIQQQQIIQQ", b, shoff + i * shentsize) for i in range(shnum)]
-    stro = secs[shstrndx][4]
-    fat = None
-    for sec in secs:
-        name = b[stro + sec[0]: b.index(b"\0", stro + sec[0])]
-        if name == b".hip_fatbin":
-            fat = b[sec[4]: sec[4] + sec[5]]
-    if fat is None:
+    secs, names = _elf_sections(b)
+    if b".hip_fatbin" not in names:
         raise ValueError("no .hip_fatbin section")
+    sec = secs[names.index(b".hip_fatbin")]
+    fat = b[sec[4]: sec[4] + sec[5]]
     magic = b"__CLANG_OFFLOAD_BUNDLE__"
     pos = fat.find(magic)
     while pos >= 0:  # bundle: magic, u64 entries, then (u64 offset, u64 size, u64 triple length, triple)
@@ -273,6 +296,26 @@ def _code_objects(path: str):
             if triple.startswith(b"hipv4-amdgcn"):
                 yield triple, fat[pos + off: pos + off + size]
         pos = fat.find(magic, pos + 1)
+
+
+def _kernel_symbols(co: bytes):
+    """(symbol name, st_info, code bytes) of every sized symbol in a code
+    object's .symtab; nothing for a code object without one."""
+    import struct
+    if co[:4] != b"\x7fELF":
+        return
+    secs, names = _elf_sections(co)
+    if b".symtab" not in names:
+        return
+    symtab = secs[names.index(b".symtab")]
+    strtab = secs[symtab[6]]  # sh_link
+    for i in range(symtab[5] // 24):
+        st_name, st_info, _other, st_shndx, st_value, st_size = struct.unpack_from("<IBBHQQ", co, symtab[4] + 24 * i)
+        if st_size and st_shndx < len(secs):  # defined in a section (not SHN_ABS / SHN_COMMON)
+            sec = secs[st_shndx]
+            start = sec[4] + (st_value - sec[3])
+            yield (co[strtab[4] + st_name: co.index(b"\0", strtab[4] + st_name)].decode(), st_info,
+                   co[start: start + st_size])
 
 
 FIXED_KERNEL = "_ZN2sf17sha1_fixed_kernelILi128ELi1ELb0EEEvPKhmjmPhNS_11PadScheduleEPj"
@@ -290,27 +333,10 @@ def kernel_code_sha256(path: str = None, symbol: str = FIXED_KERNEL) -> str:
     block rate depends on how its block part was compiled (DESIGN.md
     section 3.3b)."""
     import hashlib
-    import struct
     for _, co in _code_objects(path):
-        if co[:4] != b"\x7fELF":
-            continue
-        shoff, = struct.unpack_from("<Q", co, 0x28)
-        shentsize, shnum, shstrndx = struct.unpack_from("<HHH", co, 0x3A)
-        secs = [struct.unpack_from("<IIQQQQIIQQ", co, shoff + i * shentsize) for i in range(shnum)]
-        stro = secs[shstrndx][4]
-        names = [co[stro + s[0]: co.index(b"\0", stro + s[0])] for s in secs]
-        if b".symtab" not in names:
-            continue
-        symtab = secs[names.index(b".symtab")]
-        strtab = secs[symtab[6]]  # sh_link
-        for i in range(symtab[5] // 24):
-            st_name, st_info, st_other, st_shndx, st_value, st_size = struct.unpack_from(
-                "<IBBHQQ", co, symtab[4] + 24 * i)
-            nm = co[strtab[4] + st_name: co.index(b"\0", strtab[4] + st_name)]
-            if nm == symbol.encode() and st_size:
-                sec = secs[st_shndx]  # (name, type, flags, addr, offset, size, ...)
-                start = sec[4] + (st_value - sec[3])
-                return hashlib.sha256(co[start: start + st_size]).hexdigest()
+        for name, _info, code in _kernel_symbols(co):
+            if name == symbol:
+                return hashlib.sha256(code).hexdigest()
     raise ValueError(f"no code object defines {symbol}")
 
 
@@ -322,35 +348,9 @@ def code_object_sha256(path: str = None, kernel: bytes = b"sha1_fixed_kernel") -
     leave it unchanged; any change to the SHA-1 kernels alters it.  bench.py
     keys the PMC traffic of profiles/traffic.json on it."""
     import hashlib
-    import struct
-    with open(path or LIB_PATH, "rb") as f:
-        b = f.read()
-    if b[:4] != b"\x7fELF" or b[4] != 2:
-        raise ValueError("not an ELF64 library")
-    shoff, = struct.unpack_from("<Q", b, 0x28)
-    shentsize, shnum, shstrndx = struct.unpack_from("<HHH", b, 0x3A)
-    secs = [struct.unpack_from("<IIQQQQIIQQ", b, shoff + i * shentsize) for i in range(shnum)]
-    stro = secs[shstrndx][4]
-    fat = None
-    for sec in secs:
-        name = b[stro + sec[0]: b.index(b"\0", stro + sec[0])]
-        if name == b".hip_fatbin":
-            fat = b[sec[4]: sec[4] + sec[5]]
-    if fat is None:
-        raise ValueError("no .hip_fatbin section")
-    magic = b"__CLANG_OFFLOAD_BUNDLE__"
-    pos = fat.find(magic)
-    while pos >= 0:  # bundle: magic, u64 entries, then (u64 offset, u64 size, u64 triple length, triple)
-        n, = struct.unpack_from("<Q", fat, pos + len(magic))
-        p = pos + len(magic) + 8
-        for _ in range(n):
-            off, size, tlen = struct.unpack_from("<QQQ", fat, p)
-            triple = fat[p + 24: p + 24 + tlen]
-            p += 24 + tlen
-            co = fat[pos + off: pos + off + size]
-            if triple.startswith(b"hipv4-amdgcn") and kernel in co:
-                return hashlib.sha256(co).hexdigest()
-        pos = fat.find(magic, pos + 1)
+    for _, co in _code_objects(path):
+        if kernel in co:
+            return hashlib.sha256(co).hexdigest()
     raise ValueError(f"no code object holds {kernel!r}")
 
 

@@ -19,12 +19,13 @@ from __future__ import annotations
 
 import contextlib
 import ctypes
+import math
 from typing import Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
-from ._lib import FileDesc, check, lib, SF_ERANGE, SfError
+from ._lib import SF_ERANGE, ChainJob, FileDesc, SfError, check, lib, num_blocks, retry_enospc
 
 __all__ = [
     "num_blocks", "index_device", "index_device_blocks", "index_device_batch",
@@ -66,38 +67,79 @@ def _on(device: torch.device, stream: Optional[torch.cuda.Stream]):
                 yield
 
 
-def num_blocks(length: int, block_size: int) -> int:
-    """ceil(len / B); 0 for an empty input (no empty blocks)."""
-    return (length + block_size - 1) // block_size if length else 0
+def _ptr(t: Optional[torch.Tensor], n: Optional[int] = None) -> Optional[int]:
+    """The address the library gets for ``t``: NULL for None and for nothing
+    to read or write (``n`` elements of it in use; default: all it has)."""
+    return t.data_ptr() if t is not None and (t.numel() if n is None else n) else None
+
+
+def _out(out: Optional[torch.Tensor], name: str, shape: tuple, dtype, data: torch.Tensor) -> torch.Tensor:
+    """An output of ``shape`` on the input's device: a new tensor, or the
+    caller's once it is seen to be there, of that dtype, contiguous and large
+    enough.  Call inside ``_on``: the allocation belongs to the launch stream."""
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=data.device)
+    _require_device(out, name, dtype, data.device)
+    need = math.prod(shape)
+    if out.numel() < need:
+        raise ValueError(f"{name} holds {out.numel()} elements, need {need}")
+    return out
+
+
+def _index_fixed(data, block_size, out, weak_out, stream, weak: bool):
+    """sf_index_device_fixed / _fixed_weak: the weak form has one more output
+    and the smaller of the two capacities."""
+    _require_device(data, "data", torch.uint8)
+    n = num_blocks(data.numel(), block_size)
+    name = "sf_index_device_fixed_weak" if weak else "sf_index_device_fixed"
+    with _on(data.device, stream):
+        out = _out(out, "out", (n, 20), torch.uint8, data)
+        outs, cap = (_ptr(out, n),), out.numel() // 20
+        if weak:
+            weak_out = _out(weak_out, "weak_out", (n,), torch.int32, data)
+            outs, cap = outs + (_ptr(weak_out, n),), min(cap, weak_out.numel())
+        nb = ctypes.c_uint64(0)
+        check(getattr(lib(), name)(_ptr(data), data.numel(), block_size, *outs, cap, ctypes.byref(nb),
+                                   _stream_ptr(data, stream)), name)
+    return out, weak_out
 
 
 def index_device(data: torch.Tensor, block_size: int, out: Optional[torch.Tensor] = None,
                  stream: Optional[torch.cuda.Stream] = None) -> torch.Tensor:
     """SHA-1 of every fixed-size block of a uint8 HBM buffer -> uint8[n, 20]."""
-    _require_device(data, "data", torch.uint8)
-    n = num_blocks(data.numel(), block_size)
-    with _on(data.device, stream):
-        if out is None:
-            out = torch.empty((n, 20), dtype=torch.uint8, device=data.device)
-        else:
-            _require_device(out, "out", torch.uint8, data.device)
-            if out.numel() < 20 * n:
-                raise ValueError(f"out holds {out.numel() // 20} digests, need {n}")
-        nb = ctypes.c_uint64(0)
-        check(lib().sf_index_device_fixed(data.data_ptr() if data.numel() else None, data.numel(),
-                                          block_size, out.data_ptr() if n else None, out.numel() // 20,
-                                          ctypes.byref(nb), _stream_ptr(data, stream)),
-              "sf_index_device_fixed")
-    return out
+    return _index_fixed(data, block_size, out, None, stream, False)[0]
 
 
-def _blocks_args(data, offsets, sizes):
+def index_device_weak(data: torch.Tensor, block_size: int, out: Optional[torch.Tensor] = None,
+                      weak_out: Optional[torch.Tensor] = None, stream: Optional[torch.cuda.Stream] = None):
+    """index_device plus the opt-in weak sum: (digests uint8[n, 20], weak
+    int32[n]) where weak[i] is the zlib Adler-32 of block i (bit pattern of
+    the uint32), fused into the same kernel pass.  Not in the reference
+    (SURVEY.md 8a row a8)."""
+    return _index_fixed(data, block_size, out, weak_out, stream, True)
+
+
+def _index_blocks(data, offsets, sizes, out, check_range, stream, weak: bool):
+    """sf_index_device_blocks / _blocks_weak."""
     _require_device(data, "data", torch.uint8)
     _require_device(offsets, "offsets", torch.int64, data.device)
     _require_device(sizes, "sizes", torch.int32, data.device)
-    if sizes.numel() != offsets.numel():
+    n = offsets.numel()
+    if sizes.numel() != n:
         raise ValueError("offsets and sizes differ in length")
-    return offsets.numel()
+    name = "sf_index_device_blocks_weak" if weak else "sf_index_device_blocks"
+    with _on(data.device, stream):
+        out = _out(out, "out", (n, 20), torch.uint8, data)
+        wk = torch.empty(n, dtype=torch.int32, device=data.device) if weak else None
+        if n == 0:
+            return out, wk
+        status = torch.zeros(1, dtype=torch.int32, device=data.device) if check_range else None
+        outs = (out.data_ptr(), wk.data_ptr()) if weak else (out.data_ptr(),)
+        check(getattr(lib(), name)(_ptr(data), data.numel(), offsets.data_ptr(), sizes.data_ptr(), n, *outs,
+                                   _ptr(status), _stream_ptr(data, stream)), name)
+        if status is not None and int(status.item()) != 0:
+            raise SfError(SF_ERANGE, name)
+    return out, wk
 
 
 def index_device_blocks(data: torch.Tensor, offsets: torch.Tensor, sizes: torch.Tensor,
@@ -108,31 +150,19 @@ def index_device_blocks(data: torch.Tensor, offsets: torch.Tensor, sizes: torch.
     ``offsets`` int64 and ``sizes`` int32 tensors on the same device.  With
     ``check_range`` a block outside the buffer raises SfError(SF_ERANGE)
     (this synchronises the stream)."""
-    n = _blocks_args(data, offsets, sizes)
-    with _on(data.device, stream):
-        if out is None:
-            out = torch.empty((n, 20), dtype=torch.uint8, device=data.device)
-        else:
-            _require_device(out, "out", torch.uint8, data.device)
-            if out.numel() < 20 * n:
-                raise ValueError("out too small")
-        if n == 0:
-            return out
-        status = torch.zeros(1, dtype=torch.int32, device=data.device) if check_range else None
-        check(lib().sf_index_device_blocks(data.data_ptr() if data.numel() else None, data.numel(),
-                                           offsets.data_ptr(), sizes.data_ptr(), n, out.data_ptr(),
-                                           status.data_ptr() if status is not None else None,
-                                           _stream_ptr(data, stream)),
-              "sf_index_device_blocks")
-        if status is not None and int(status.item()) != 0:
-            raise SfError(SF_ERANGE, "sf_index_device_blocks")
-    return out
+    return _index_blocks(data, offsets, sizes, out, check_range, stream, False)[0]
+
+
+def index_device_blocks_weak(data: torch.Tensor, offsets: torch.Tensor, sizes: torch.Tensor,
+                             check_range: bool = True, stream: Optional[torch.cuda.Stream] = None):
+    """index_device_blocks plus the opt-in Adler-32 per block (0 for a block
+    outside the buffer) -> (digests uint8[n, 20], weak int32[n])."""
+    return _index_blocks(data, offsets, sizes, None, check_range, stream, True)
 
 
 def zpaq_segment_len(max_size: int) -> int:
     """Segment length of the device ZPAQ cutter: lcm(max_size, 32) bytes, a
     function of max_size only (include/syncfast_amd.h, sf_cut_device_zpaq)."""
-    import math
     return max_size // math.gcd(max_size, 32) * 32
 
 
@@ -148,29 +178,24 @@ def _zpaq_call(data, bits, max_size, stream, digests: bool, blocks_hash: bool):
     """sf_cut_device_zpaq / sf_index_device_zpaq with outputs sized from a
     guess (len >> (bits - 1) + 16 blocks) and once more from the need the
     library reports with SF_ENOSPC."""
-    from ._lib import SF_ENOSPC
     _require_device(data, "data", torch.uint8)
     n = data.numel()
-    cap = min(n, (n >> max(bits - 1, 0)) + n // max_size + 16)
     bh = (ctypes.c_uint8 * 20)() if blocks_hash else None
     nb = ctypes.c_uint64(0)
+
+    def call(cap):
+        offs = torch.empty(cap, dtype=torch.int64, device=data.device)
+        sizes = torch.empty(cap, dtype=torch.int32, device=data.device)
+        dig = torch.empty((cap, 20), dtype=torch.uint8, device=data.device) if digests else None
+        args = (_ptr(data), n, bits, max_size, _ptr(offs), _ptr(sizes))
+        if digests:
+            rc = lib().sf_index_device_zpaq(*args, _ptr(dig), cap, ctypes.byref(nb), bh, _stream_ptr(data, stream))
+        else:
+            rc = lib().sf_cut_device_zpaq(*args, cap, ctypes.byref(nb), _stream_ptr(data, stream))
+        return rc, nb.value, (offs, sizes, dig)
     with _on(data.device, stream):
-        for _attempt in range(2):
-            offs = torch.empty(cap, dtype=torch.int64, device=data.device)
-            sizes = torch.empty(cap, dtype=torch.int32, device=data.device)
-            dig = torch.empty((cap, 20), dtype=torch.uint8, device=data.device) if digests else None
-            args = (data.data_ptr() if n else None, n, bits, max_size, offs.data_ptr() if cap else None,
-                    sizes.data_ptr() if cap else None)
-            if digests:
-                rc = lib().sf_index_device_zpaq(*args, dig.data_ptr() if cap else None, cap, ctypes.byref(nb), bh,
-                                                _stream_ptr(data, stream))
-            else:
-                rc = lib().sf_cut_device_zpaq(*args, cap, ctypes.byref(nb), _stream_ptr(data, stream))
-            if rc != SF_ENOSPC:
-                break
-            cap = nb.value
-        check(rc, "sf_index_device_zpaq" if digests else "sf_cut_device_zpaq")
-    k = nb.value
+        k, (offs, sizes, dig) = retry_enospc(call, min(n, (n >> max(bits - 1, 0)) + n // max_size + 16), 2,
+                                             "sf_index_device_zpaq" if digests else "sf_cut_device_zpaq")
     return offs[:k], sizes[:k], (dig[:k] if digests else None), (bytes(bh) if blocks_hash else None)
 
 
@@ -192,53 +217,6 @@ def index_device_zpaq(data: torch.Tensor, bits: int = 13, max_size: int = 32768,
     Returns (offsets int64[n], sizes int32[n], digests uint8[n, 20],
     blocks_hash or None)."""
     return _zpaq_call(data, bits, max_size, stream, True, blocks_hash)
-
-
-def index_device_weak(data: torch.Tensor, block_size: int, out: Optional[torch.Tensor] = None,
-                      weak_out: Optional[torch.Tensor] = None, stream: Optional[torch.cuda.Stream] = None):
-    """index_device plus the opt-in weak sum: (digests uint8[n, 20], weak
-    int32[n]) where weak[i] is the zlib Adler-32 of block i (bit pattern of
-    the uint32), fused into the same kernel pass.  Not in the reference
-    (SURVEY.md 8a row a8)."""
-    _require_device(data, "data", torch.uint8)
-    n = num_blocks(data.numel(), block_size)
-    with _on(data.device, stream):
-        if out is None:
-            out = torch.empty((n, 20), dtype=torch.uint8, device=data.device)
-        if weak_out is None:
-            weak_out = torch.empty(n, dtype=torch.int32, device=data.device)
-        _require_device(out, "out", torch.uint8, data.device)
-        _require_device(weak_out, "weak_out", torch.int32, data.device)
-        if out.numel() < 20 * n or weak_out.numel() < n:
-            raise ValueError(f"outputs too small for {n} blocks")
-        nb = ctypes.c_uint64(0)
-        check(lib().sf_index_device_fixed_weak(data.data_ptr() if data.numel() else None, data.numel(), block_size,
-                                               out.data_ptr() if n else None, weak_out.data_ptr() if n else None,
-                                               min(out.numel() // 20, weak_out.numel()), ctypes.byref(nb),
-                                               _stream_ptr(data, stream)),
-              "sf_index_device_fixed_weak")
-    return out, weak_out
-
-
-def index_device_blocks_weak(data: torch.Tensor, offsets: torch.Tensor, sizes: torch.Tensor,
-                             check_range: bool = True, stream: Optional[torch.cuda.Stream] = None):
-    """index_device_blocks plus the opt-in Adler-32 per block (0 for a block
-    outside the buffer) -> (digests uint8[n, 20], weak int32[n])."""
-    n = _blocks_args(data, offsets, sizes)
-    with _on(data.device, stream):
-        out = torch.empty((n, 20), dtype=torch.uint8, device=data.device)
-        weak = torch.empty(n, dtype=torch.int32, device=data.device)
-        if n == 0:
-            return out, weak
-        status = torch.zeros(1, dtype=torch.int32, device=data.device) if check_range else None
-        check(lib().sf_index_device_blocks_weak(data.data_ptr() if data.numel() else None, data.numel(),
-                                                offsets.data_ptr(), sizes.data_ptr(), n, out.data_ptr(),
-                                                weak.data_ptr(), status.data_ptr() if status is not None else None,
-                                                _stream_ptr(data, stream)),
-              "sf_index_device_blocks_weak")
-        if status is not None and int(status.item()) != 0:
-            raise SfError(SF_ERANGE, "sf_index_device_blocks_weak")
-    return out, weak
 
 
 def index_device_batch(data: torch.Tensor, files: Sequence[Tuple[int, int]], block_size: int,
@@ -265,31 +243,15 @@ def index_device_batch(data: torch.Tensor, files: Sequence[Tuple[int, int]], blo
         descs[i].offset, descs[i].len = int(o), int(ln)
         total += num_blocks(int(ln), block_size)
     with _on(data.device, stream):
-        if out is None:
-            out = torch.empty((total, 20), dtype=torch.uint8, device=data.device)
-        else:
-            _require_device(out, "out", torch.uint8, data.device)
-            if out.numel() < 20 * total:
-                raise ValueError("out too small")
-        dig = out
-        fh = None
-        if file_hashes and nf:
-            if hashes_out is not None:
-                _require_device(hashes_out, "hashes_out", torch.uint8, data.device)
-            fh = hashes_out if hashes_out is not None else torch.empty((nf, 20), dtype=torch.uint8, device=data.device)
-            if fh.numel() < 20 * nf:
-                raise ValueError("hashes_out too small")
+        dig = _out(out, "out", (total, 20), torch.uint8, data)
+        fh = _out(hashes_out, "hashes_out", (nf, 20), torch.uint8, data) if file_hashes and nf else None
         first = np.zeros(nf + 1, np.uint64)
         nb = ctypes.c_uint64(0)
         if status is not None:
             _require_device(status, "status", torch.int32, data.device)
-        check(lib().sf_index_device_batch(data.data_ptr() if data.numel() else None, data.numel(), descs, nf,
-                                          block_size, dig.data_ptr() if total else None, dig.numel() // 20,
-                                          fh.data_ptr() if fh is not None else None,
-                                          first.ctypes.data, ctypes.byref(nb),
-                                          status.data_ptr() if status is not None else None,
-                                          _stream_ptr(data, stream)),
-              "sf_index_device_batch")
+        check(lib().sf_index_device_batch(_ptr(data), data.numel(), descs, nf, block_size, _ptr(dig, total),
+                                          dig.numel() // 20, _ptr(fh), first.ctypes.data, ctypes.byref(nb),
+                                          _ptr(status), _stream_ptr(data, stream)), "sf_index_device_batch")
     return dig, first.astype(np.int64), fh
 
 
@@ -325,21 +287,16 @@ class BatchStream:
         self._states = None
 
     def _job(self, part, entry, state=None):
-        from ._lib import ChainJob
         d, h = entry[0], entry[1]
-        return ChainJob(d.data_ptr(), self.n_files, part, self.nbf, state.data_ptr() if state is not None else None,
-                        h.data_ptr() if part != 1 else None)
+        return ChainJob(d.data_ptr(), self.n_files, part, self.nbf, _ptr(state), h.data_ptr() if part != 1 else None)
 
     def _launch(self, data, digests, jobs, ref, cols=None):
-        from ._lib import ChainJob
         arr = (ChainJob * max(len(jobs), 1))(*jobs)
         lo, hi = cols if cols is not None else (0, self.nbf)
         with _on(ref.device, self.stream):
             check(lib().sf_index_device_batch_chained_cols(
-                data.data_ptr() if data is not None else None, self.n_files if data is not None else 0,
-                self.file_len, self.block_size, lo, hi, digests.data_ptr() if digests is not None else None,
-                arr, len(jobs), _stream_ptr(ref, self.stream)),
-                "sf_index_device_batch_chained_cols")
+                _ptr(data), self.n_files if data is not None else 0, self.file_len, self.block_size, lo, hi,
+                _ptr(digests), arr, len(jobs), _stream_ptr(ref, self.stream)), "sf_index_device_batch_chained_cols")
 
     def _step_jobs(self):
         """Chain jobs for the next launch; advances the pipeline state."""
@@ -426,6 +383,19 @@ class BatchStream:
         return out
 
 
+def _receive_outputs(run: torch.Tensor, lookup: bool):
+    """(capacity, digests uint8[cap, 20], sizes int32[cap]) for the FILE_BLOCK
+    messages of ``run`` and, with ``lookup``, (offsets, rows) int64[cap] too.
+    Call inside ``_on``."""
+    cap = run.numel() // 34 + 1  # a message is at least 34 bytes
+    digests = torch.empty((cap, 20), dtype=torch.uint8, device=run.device)
+    sizes = torch.empty(cap, dtype=torch.int32, device=run.device)
+    if not lookup:
+        return cap, digests, sizes
+    offsets = torch.empty(cap, dtype=torch.int64, device=run.device)
+    return cap, digests, sizes, offsets, torch.empty(cap, dtype=torch.int64, device=run.device)
+
+
 class BlockSet:
     """The receiving side's block lookup, on the device (sf_block_set_*).
 
@@ -453,10 +423,8 @@ class BlockSet:
         self.table, self.present, self.stream = table, present, stream
         self._h = ctypes.c_void_p()
         with _on(table.device, stream):
-            check(lib().sf_block_set_build(table.data_ptr() if n else None,
-                                           present.data_ptr() if present is not None and n else None, n,
-                                           ctypes.byref(self._h), _stream_ptr(table, stream)),
-                  "sf_block_set_build")
+            check(lib().sf_block_set_build(_ptr(table), _ptr(present), n, ctypes.byref(self._h),
+                                           _stream_ptr(table, stream)), "sf_block_set_build")
 
     def lookup(self, digests: torch.Tensor) -> torch.Tensor:
         _require_device(digests, "digests", torch.uint8, self.table.device)
@@ -489,17 +457,11 @@ class BlockSet:
             raise ValueError("run must be a flat uint8 tensor")
         if not self._h:
             raise ValueError("BlockSet is closed")
-        nb = run.numel()
-        cap = nb // 34 + 1  # a message is at least 34 bytes
         n, consumed, end = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
         stop = ctypes.c_int(0)
-        dev = self.table.device
-        with _on(dev, self.stream):
-            digests = torch.empty((cap, 20), dtype=torch.uint8, device=dev)
-            sizes = torch.empty(cap, dtype=torch.int32, device=dev)
-            offsets = torch.empty(cap, dtype=torch.int64, device=dev)
-            rows = torch.empty(cap, dtype=torch.int64, device=dev)
-            check(lib().sf_receive_blocks_device(self._h, run.data_ptr() if nb else None, nb, int(base_offset),
+        with _on(self.table.device, self.stream):
+            cap, digests, sizes, offsets, rows = _receive_outputs(run, True)
+            check(lib().sf_receive_blocks_device(self._h, _ptr(run), run.numel(), int(base_offset),
                                                  digests.data_ptr(), sizes.data_ptr(), offsets.data_ptr(),
                                                  rows.data_ptr(), cap, ctypes.byref(n), ctypes.byref(consumed),
                                                  ctypes.byref(stop), ctypes.byref(end),
@@ -587,7 +549,7 @@ def fill_splitmix(out: torch.Tensor, seed: int, start: int = 0,
     splitmix64 stream `seed` (the synthetic input of bench.py / tests)."""
     _require_device(out, "out", torch.uint8)
     with torch.cuda.device(out.device):
-        check(lib().sf_fill_splitmix_device(out.data_ptr() if out.numel() else None, out.numel(),
+        check(lib().sf_fill_splitmix_device(_ptr(out), out.numel(),
                                             seed & 0xFFFFFFFFFFFFFFFF, start, _stream_ptr(out, stream)),
               "sf_fill_splitmix_device")
     return out

@@ -14,7 +14,7 @@ from typing import List, Sequence, Tuple
 
 import numpy as np
 
-from ._lib import SF_EINVAL, SF_EIO, SF_ENOSPC, BlockSig, FileStamp, check, lib
+from ._lib import SF_EINVAL, SF_EIO, BlockSig, ChunkerOps, FileStamp, check, lib, num_blocks, retry_enospc
 
 SIG_DTYPE = np.dtype([("offset", "<u8"), ("size", "<u4"), ("sha1", "u1", (20,))], align=True)
 assert SIG_DTYPE.itemsize == ctypes.sizeof(BlockSig) == 32
@@ -26,15 +26,53 @@ def _u8(data) -> np.ndarray:
     return np.frombuffer(memoryview(data), dtype=np.uint8)
 
 
+def _ptr(a: np.ndarray):
+    return a.ctypes.data if a.size else None
+
+
+def _list(offsets, sizes) -> Tuple[np.ndarray, np.ndarray, int]:
+    """An explicit block list as the library takes it: flat contiguous
+    uint64 offsets and uint32 sizes, and their common length."""
+    offs = np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1)
+    szs = np.ascontiguousarray(sizes, dtype=np.uint32).reshape(-1)
+    if offs.size != szs.size:
+        raise ValueError("offsets and sizes differ in length")
+    return offs, szs, offs.size
+
+
+def _rows(n: int):
+    """Room for n signature rows (never an empty allocation) and its pointer."""
+    out = np.zeros(max(n, 1), SIG_DTYPE)
+    return out, out.ctypes.data_as(ctypes.POINTER(BlockSig))
+
+
+def _digest():
+    return (ctypes.c_uint8 * 20)()
+
+
+def _take_rows(rows, n: int, free=None) -> np.ndarray:
+    """The n rows the library malloc'd at ``rows`` as an array of our own;
+    the library's buffer is freed (sf_free_rows) whatever happens."""
+    try:
+        out = np.zeros(n, SIG_DTYPE)
+        if n:
+            ctypes.memmove(out.ctypes.data, rows, n * SIG_DTYPE.itemsize)
+        return out
+    finally:
+        (free or lib().sf_free_rows)(rows)
+
+
+def _ref(stamp: FileStamp):
+    return ctypes.byref(stamp) if stamp is not None else None
+
+
 def index_buffer(data, block_size: int) -> np.ndarray:
     """Fixed-size block signatures of a host buffer -> SIG_DTYPE rows."""
     a = _u8(data)
-    n = (a.size + block_size - 1) // block_size if a.size else 0
-    out = np.zeros(max(n, 1), SIG_DTYPE)
+    n = num_blocks(a.size, block_size)
+    out, p = _rows(n)
     nout = ctypes.c_uint64(0)
-    check(lib().sf_index_buffer(a.ctypes.data if a.size else None, a.size, block_size,
-                                out.ctypes.data_as(ctypes.POINTER(BlockSig)), n, ctypes.byref(nout)),
-          "sf_index_buffer")
+    check(lib().sf_index_buffer(_ptr(a), a.size, block_size, p, n, ctypes.byref(nout)), "sf_index_buffer")
     return out[:n]
 
 
@@ -45,17 +83,9 @@ def index_buffer_blocks(data, offsets, sizes) -> Tuple[np.ndarray, bytes]:
     (sf_index_buffer_blocks).  SF_ERANGE / SF_EINVAL for a block past the end
     / offsets that go backwards, before anything runs."""
     a = _u8(data)
-    offs = np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1)
-    szs = np.ascontiguousarray(sizes, dtype=np.uint32).reshape(-1)
-    if offs.size != szs.size:
-        raise ValueError("offsets and sizes differ in length")
-    n = offs.size
-    out = np.zeros(max(n, 1), SIG_DTYPE)
-    bh = (ctypes.c_uint8 * 20)()
-    check(lib().sf_index_buffer_blocks(a.ctypes.data if a.size else None, a.size,
-                                       offs.ctypes.data if n else None, szs.ctypes.data if n else None, n,
-                                       out.ctypes.data_as(ctypes.POINTER(BlockSig)), bh),
-          "sf_index_buffer_blocks")
+    offs, szs, n = _list(offsets, sizes)
+    (out, p), bh = _rows(n), _digest()
+    check(lib().sf_index_buffer_blocks(_ptr(a), a.size, _ptr(offs), _ptr(szs), n, p, bh), "sf_index_buffer_blocks")
     return out[:n], bytes(bh)
 
 
@@ -63,16 +93,9 @@ def index_file_blocks(path, offsets, sizes) -> Tuple[np.ndarray, bytes]:
     """As index_buffer_blocks over a regular file on disk, read again window
     by window with pread (sf_index_file_blocks): the boundaries came from a
     chunker that streamed the file; the file is never held whole in memory."""
-    offs = np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1)
-    szs = np.ascontiguousarray(sizes, dtype=np.uint32).reshape(-1)
-    if offs.size != szs.size:
-        raise ValueError("offsets and sizes differ in length")
-    n = offs.size
-    out = np.zeros(max(n, 1), SIG_DTYPE)
-    bh = (ctypes.c_uint8 * 20)()
-    check(lib().sf_index_file_blocks(os.fsencode(path), offs.ctypes.data if n else None,
-                                     szs.ctypes.data if n else None, n,
-                                     out.ctypes.data_as(ctypes.POINTER(BlockSig)), bh),
+    offs, szs, n = _list(offsets, sizes)
+    (out, p), bh = _rows(n), _digest()
+    check(lib().sf_index_file_blocks(os.fsencode(path), _ptr(offs), _ptr(szs), n, p, bh),
           f"sf_index_file_blocks({os.fsdecode(path)})")
     return out[:n], bytes(bh)
 
@@ -91,30 +114,19 @@ def index_fd_blocks(fd: int, offsets, sizes, stamp: FileStamp = None) -> Tuple[n
     the file the chunker cut even if another file was renamed over its path.
     `stamp` (file_stamp before chunking): SfError SF_EAGAIN if the file
     differs from it at the call or changes before the last window is read."""
-    offs = np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1)
-    szs = np.ascontiguousarray(sizes, dtype=np.uint32).reshape(-1)
-    if offs.size != szs.size:
-        raise ValueError("offsets and sizes differ in length")
-    n = offs.size
-    out = np.zeros(max(n, 1), SIG_DTYPE)
-    bh = (ctypes.c_uint8 * 20)()
-    check(lib().sf_index_fd_blocks(int(fd), ctypes.byref(stamp) if stamp is not None else None,
-                                   offs.ctypes.data if n else None, szs.ctypes.data if n else None, n,
-                                   out.ctypes.data_as(ctypes.POINTER(BlockSig)), bh),
-          "sf_index_fd_blocks")
+    offs, szs, n = _list(offsets, sizes)
+    (out, p), bh = _rows(n), _digest()
+    check(lib().sf_index_fd_blocks(int(fd), _ref(stamp), _ptr(offs), _ptr(szs), n, p, bh), "sf_index_fd_blocks")
     return out[:n], bytes(bh)
 
 
 def index_fd_fixed(fd: int, block_size: int, stamp: FileStamp = None) -> Tuple[np.ndarray, bytes]:
     """Fixed tiling of the regular file open on fd (sf_index_fd_fixed), with
     the same stamp checks as index_fd_blocks."""
-    size = os.fstat(int(fd)).st_size
-    n = (size + block_size - 1) // block_size if size else 0
-    out = np.zeros(max(n, 1), SIG_DTYPE)
+    n = num_blocks(os.fstat(int(fd)).st_size, block_size)
+    (out, p), bh = _rows(n), _digest()
     nout = ctypes.c_uint64(0)
-    bh = (ctypes.c_uint8 * 20)()
-    check(lib().sf_index_fd_fixed(int(fd), ctypes.byref(stamp) if stamp is not None else None, block_size,
-                                  out.ctypes.data_as(ctypes.POINTER(BlockSig)), n, ctypes.byref(nout), bh),
+    check(lib().sf_index_fd_fixed(int(fd), _ref(stamp), block_size, p, n, ctypes.byref(nout), bh),
           "sf_index_fd_fixed")
     return out[:nout.value], bytes(bh)
 
@@ -139,30 +151,23 @@ def index_file(path, block_size: int) -> Tuple[np.ndarray, bytes]:
             return index_fd(fd, block_size)
         finally:
             os.close(fd)
-    size = st.st_size
-    n = (size + block_size - 1) // block_size if size else 0
-    nout = ctypes.c_uint64(0)
-    bh = (ctypes.c_uint8 * 20)()
-    for _attempt in range(4):
-        out = np.zeros(max(n, 1), SIG_DTYPE)
-        rc = lib().sf_index_file(os.fsencode(path), block_size, out.ctypes.data_as(ctypes.POINTER(BlockSig)),
-                                 n, ctypes.byref(nout), bh)
-        if rc == SF_ENOSPC and nout.value > n:
-            n = nout.value
-            continue
-        break
-    check(rc, "sf_index_file")
-    return out[:nout.value], bytes(bh)
+    nout, bh = ctypes.c_uint64(0), _digest()
+
+    def call(cap):
+        out, p = _rows(cap)
+        rc = lib().sf_index_file(os.fsencode(path), block_size, p, cap, ctypes.byref(nout), bh)
+        return rc, nout.value, out
+    n, out = retry_enospc(call, num_blocks(st.st_size, block_size), 4, "sf_index_file")
+    return out[:n], bytes(bh)
 
 
 def index_file_range(path, start: int, length: int, block_size: int) -> np.ndarray:
     """Rows of bytes [start, start+length) of a file (one shard of it; start a
     multiple of block_size), offsets relative to the file (sf_index_file_range)."""
-    n = (length + block_size - 1) // block_size if length else 0
-    out = np.zeros(max(n, 1), SIG_DTYPE)
+    n = num_blocks(length, block_size)
+    out, p = _rows(n)
     nout = ctypes.c_uint64(0)
-    check(lib().sf_index_file_range(os.fsencode(path), start, length, block_size,
-                                    out.ctypes.data_as(ctypes.POINTER(BlockSig)), n, ctypes.byref(nout)),
+    check(lib().sf_index_file_range(os.fsencode(path), start, length, block_size, p, n, ctypes.byref(nout)),
           "sf_index_file_range")
     return out[:nout.value]
 
@@ -171,18 +176,9 @@ def index_fd(fd: int, block_size: int) -> Tuple[np.ndarray, bytes]:
     """Signatures of everything readable from an open descriptor (a pipe, a
     FIFO, ...) to EOF + its blocks_hash (sf_index_fd: sequential route, rows
     in a library-grown buffer)."""
-    rows = ctypes.POINTER(BlockSig)()
-    nout = ctypes.c_uint64(0)
-    bh = (ctypes.c_uint8 * 20)()
+    rows, nout, bh = ctypes.POINTER(BlockSig)(), ctypes.c_uint64(0), _digest()
     check(lib().sf_index_fd(int(fd), block_size, ctypes.byref(rows), ctypes.byref(nout), bh), "sf_index_fd")
-    try:
-        n = nout.value
-        out = np.zeros(n, SIG_DTYPE)
-        if n:
-            ctypes.memmove(out.ctypes.data, rows, n * SIG_DTYPE.itemsize)
-    finally:
-        lib().sf_free_rows(rows)
-    return out, bytes(bh)
+    return _take_rows(rows, nout.value), bytes(bh)
 
 
 def index_files(paths: Sequence, block_size: int, stage_bytes: int = 0) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
@@ -199,19 +195,19 @@ def index_files(paths: Sequence, block_size: int, stage_bytes: int = 0) -> Tuple
     first = np.zeros(n + 1, np.uint64)
     hashes = np.zeros((max(n, 1), 20), np.uint8)
     need, bad = ctypes.c_uint64(0), ctypes.c_uint32(0)
-    cap = 0
-    while True:  # a file may grow between the sizing call and the real one
-        out = np.zeros(max(cap, 1), SIG_DTYPE)
-        rc = lib().sf_index_files(arr, n, block_size, stage_bytes, out.ctypes.data_as(ctypes.POINTER(BlockSig)),
-                                  cap, first.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), hashes.ctypes.data,
+
+    def call(cap):  # cap 0 is the sizing call; a file may grow between it and the real one
+        out, p = _rows(cap)
+        rc = lib().sf_index_files(arr, n, block_size, stage_bytes, p, cap,
+                                  first.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), hashes.ctypes.data,
                                   ctypes.byref(need), ctypes.byref(bad))
-        if rc == SF_ENOSPC and need.value > cap:
-            cap = need.value
-            continue
-        where = f"sf_index_files: {os.fsdecode(enc[bad.value])}" if rc in (SF_EIO, SF_EINVAL) and bad.value < n \
-            else "sf_index_files"
-        check(rc, where)
-        return out[:need.value], first, hashes[:n]
+        return rc, need.value, out
+
+    def where(rc):
+        named = rc in (SF_EIO, SF_EINVAL) and bad.value < n
+        return f"sf_index_files: {os.fsdecode(enc[bad.value])}" if named else "sf_index_files"
+    total, out = retry_enospc(call, 0, 4, where)
+    return out[:total], first, hashes[:n]
 
 
 def index_fds_blocks(fds: Sequence[int], lists: Sequence[Tuple[object, object]], stamps: Sequence = None,
@@ -231,29 +227,21 @@ def index_fds_blocks(fds: Sequence[int], lists: Sequence[Tuple[object, object]],
     n = len(fds)
     if len(lists) != n or (stamps is not None and len(stamps) != n):
         raise ValueError("fds, lists and stamps differ in length")
-    offs, szs = [], []
-    for o, z in lists:
-        o = np.ascontiguousarray(o, dtype=np.uint64).reshape(-1)
-        z = np.ascontiguousarray(z, dtype=np.uint32).reshape(-1)
-        if o.size != z.size:
-            raise ValueError("offsets and sizes differ in length")
-        offs.append(o)
-        szs.append(z)
-    nb = np.array([o.size for o in offs] or [0], np.uint64)
-    po = (ctypes.c_void_p * max(n, 1))(*[o.ctypes.data if o.size else None for o in offs])
-    pz = (ctypes.c_void_p * max(n, 1))(*[z.ctypes.data if z.size else None for z in szs])
+    cut = [_list(o, z) for o, z in lists]
+    nb = np.array([k for _o, _z, k in cut] or [0], np.uint64)
+    po = (ctypes.c_void_p * max(n, 1))(*[_ptr(o) for o, _z, _k in cut])
+    pz = (ctypes.c_void_p * max(n, 1))(*[_ptr(z) for _o, z, _k in cut])
     fda = np.array(list(fds) or [0], np.int32)
     st = None
     if stamps is not None:
         st = (FileStamp * max(n, 1))(*stamps)
     total = int(nb[:n].sum()) if n else 0
-    out = np.zeros(max(total, 1), SIG_DTYPE)
+    out, p = _rows(total)
     first = np.zeros(n + 1, np.uint64)
     hashes = np.zeros((max(n, 1), 20), np.uint8)
     status = np.zeros(max(n, 1), np.int32)
     bad = ctypes.c_uint32(0)
-    rc = lib().sf_index_fds_blocks(fda.ctypes.data, st, n, po, pz, nb.ctypes.data, stage_bytes,
-                                   out.ctypes.data_as(ctypes.POINTER(BlockSig)), total,
+    rc = lib().sf_index_fds_blocks(fda.ctypes.data, st, n, po, pz, nb.ctypes.data, stage_bytes, p, total,
                                    first.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), hashes.ctypes.data,
                                    status.ctypes.data, ctypes.byref(bad))
     if rc != 0 and not (n and bad.value < n and status[bad.value] == rc):
@@ -290,18 +278,10 @@ def index_fd_cut(fd: int, ops, threads: int = 0, stamp: FileStamp = None) -> Tup
     caller's chunker (``ops``: the address of an sf_chunker_ops) on
     ``threads`` threads, the file read once (sf_index_fd_cut).  Returns
     (rows, blocks_hash); SfError(SF_EAGAIN) if the file changed."""
-    p = ctypes.POINTER(BlockSig)()
-    n = ctypes.c_uint64(0)
-    bh = (ctypes.c_uint8 * 20)()
-    check(lib().sf_index_fd_cut(fd, ctypes.byref(stamp) if stamp is not None else None, ops, threads,
-                                ctypes.byref(p), ctypes.byref(n), bh), "sf_index_fd_cut")
-    try:
-        rows = np.zeros(n.value, SIG_DTYPE)
-        if n.value:
-            ctypes.memmove(rows.ctypes.data, p, n.value * SIG_DTYPE.itemsize)
-    finally:
-        lib().sf_free_rows(p)
-    return rows, bytes(bh)
+    p, n, bh = ctypes.POINTER(BlockSig)(), ctypes.c_uint64(0), _digest()
+    check(lib().sf_index_fd_cut(fd, _ref(stamp), ops, threads, ctypes.byref(p), ctypes.byref(n), bh),
+          "sf_index_fd_cut")
+    return _take_rows(p, n.value), bytes(bh)
 
 
 def zpaq_cut_buffer(data, bits: int = 13, max_size: int = 32768) -> Tuple[np.ndarray, np.ndarray]:
@@ -309,25 +289,21 @@ def zpaq_cut_buffer(data, bits: int = 13, max_size: int = 32768) -> Tuple[np.nda
     cut sequentially on this thread (sf_zpaq_cut_buffer, the library's
     definition of the boundaries): (offsets uint64, sizes uint32)."""
     a = _u8(data)
-    cap = max(16, a.size >> max(bits - 2, 0))
     n = ctypes.c_uint64(0)
-    for _attempt in range(2):
+
+    def call(cap):
         offs, sizes = np.zeros(cap, np.uint64), np.zeros(cap, np.uint32)
-        rc = lib().sf_zpaq_cut_buffer(a.ctypes.data if a.size else None, a.size, bits, max_size, offs.ctypes.data,
-                                      sizes.ctypes.data, cap, ctypes.byref(n))
-        if rc != SF_ENOSPC:
-            break
-        cap = n.value
-    check(rc, "sf_zpaq_cut_buffer")
-    return offs[:n.value], sizes[:n.value]
+        rc = lib().sf_zpaq_cut_buffer(_ptr(a), a.size, bits, max_size, offs.ctypes.data, sizes.ctypes.data, cap,
+                                      ctypes.byref(n))
+        return rc, n.value, (offs, sizes)
+    k, (offs, sizes) = retry_enospc(call, max(16, a.size >> max(bits - 2, 0)), 2, "sf_zpaq_cut_buffer")
+    return offs[:k], sizes[:k]
 
 
-class ZpaqOps(ctypes.Structure):
+class ZpaqOps(ChunkerOps):
     """An sf_chunker_ops filled by sf_zpaq_chunker_ops: the reference's
     chunker for sf_cut_fd / sf_index_fd_cut (``.address`` is what they take).
     The parameters live in its ctx field; nothing to release."""
-    _fields_ = [("create", ctypes.c_void_p), ("next", ctypes.c_void_p), ("destroy", ctypes.c_void_p),
-                ("ctx", ctypes.c_void_p)]
 
     def __init__(self, bits: int = 13, max_size: int = 32768):
         super().__init__()
@@ -343,18 +319,10 @@ def index_fd_zpaq(fd: int, bits: int = 13, max_size: int = 32768, stamp: FileSta
     host chunker: read once, cut and hashed on the device by windows
     (sf_index_fd_zpaq).  Returns (rows, blocks_hash); SfError(SF_EAGAIN) if
     the file changed."""
-    p = ctypes.POINTER(BlockSig)()
-    n = ctypes.c_uint64(0)
-    bh = (ctypes.c_uint8 * 20)()
-    check(lib().sf_index_fd_zpaq(fd, ctypes.byref(stamp) if stamp is not None else None, bits, max_size,
-                                 ctypes.byref(p), ctypes.byref(n), bh), "sf_index_fd_zpaq")
-    try:
-        rows = np.zeros(n.value, SIG_DTYPE)
-        if n.value:
-            ctypes.memmove(rows.ctypes.data, p, n.value * SIG_DTYPE.itemsize)
-    finally:
-        lib().sf_free_rows(p)
-    return rows, bytes(bh)
+    p, n, bh = ctypes.POINTER(BlockSig)(), ctypes.c_uint64(0), _digest()
+    check(lib().sf_index_fd_zpaq(fd, _ref(stamp), bits, max_size, ctypes.byref(p), ctypes.byref(n), bh),
+          "sf_index_fd_zpaq")
+    return _take_rows(p, n.value), bytes(bh)
 
 
 def shard_range(file_len: int, block_size: int, n_shards: int, shard: int) -> Tuple[int, int]:
@@ -371,20 +339,15 @@ def index_file_multi(path, block_size: int, n_devices: int = 0) -> Tuple[np.ndar
     shard r read and hashed on device r by a host thread of its own, rows in
     file order, blocks_hash over all digests.  n_devices = 0: every visible
     device."""
-    size = os.stat(path).st_size
-    n = (size + block_size - 1) // block_size if size else 0
-    need = ctypes.c_uint64(0)
-    bh = (ctypes.c_uint8 * 20)()
-    for _attempt in range(4):  # the file may grow between the stat and the call
-        out = np.zeros(max(n, 1), SIG_DTYPE)
-        rc = lib().sf_index_file_multi(os.fsencode(path), block_size, n_devices,
-                                       out.ctypes.data_as(ctypes.POINTER(BlockSig)), n, ctypes.byref(need), bh)
-        if rc == SF_ENOSPC and need.value > n:
-            n = need.value
-            continue
-        break
-    check(rc, f"sf_index_file_multi({os.fsdecode(path)})")
-    return out[:need.value], bytes(bh)
+    need, bh = ctypes.c_uint64(0), _digest()
+
+    def call(cap):  # the file may grow between the stat and the call
+        out, p = _rows(cap)
+        rc = lib().sf_index_file_multi(os.fsencode(path), block_size, n_devices, p, cap, ctypes.byref(need), bh)
+        return rc, need.value, out
+    n, out = retry_enospc(call, num_blocks(os.stat(path).st_size, block_size), 4,
+                          f"sf_index_file_multi({os.fsdecode(path)})")
+    return out[:n], bytes(bh)
 
 
 def blocks_hash(digests) -> bytes:

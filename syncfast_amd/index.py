@@ -63,7 +63,7 @@ from typing import Callable, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import host
-from ._lib import SF_EAGAIN, SfError, same_stamp
+from ._lib import SF_EAGAIN, ChunkerOps, SfError, same_stamp
 from .digest import HashDigest
 from .timestamp import DateTimeUtc
 
@@ -192,14 +192,6 @@ class BoundaryChunker:
         self.stream = stream
 
 
-class _ChunkerOps(ctypes.Structure):
-    """sf_chunker_ops (include/syncfast_amd.h)."""
-    _fields_ = [("create", ctypes.CFUNCTYPE(ctypes.c_void_p, ctypes.c_void_p)),
-                ("next", ctypes.CFUNCTYPE(ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t)),
-                ("destroy", ctypes.CFUNCTYPE(None, ctypes.c_void_p)),
-                ("ctx", ctypes.c_void_p)]
-
-
 class NativeChunker(BoundaryChunker):
     """The reference's mode with a native chunker: ``ops`` is the address of
     an sf_chunker_ops (create / next / destroy in C: cdchunking's ZPAQ on the
@@ -233,7 +225,7 @@ class NativeChunker(BoundaryChunker):
     def _cut_bytes(self, raw: bytes) -> List[int]:
         """The chunker over bytes in memory, driven from here through its
         three functions (the one-pass fallback of index_file)."""
-        ops = _ChunkerOps.from_address(self.ops)
+        ops = ChunkerOps.from_address(self.ops)
         ch = ops.create(ops.ctx)
         if not ch:
             raise MemoryError("chunker create failed")

@@ -220,8 +220,7 @@ def index_file_blocks_sharded(path, offsets, sizes, group: Optional[dist.Process
     rank = dist.get_rank(group)
     is_dst = dist.get_rank() == dst
     where = device if device is not None else torch.device("cpu")
-    offs = np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1)
-    szs = np.ascontiguousarray(sizes, dtype=np.uint32).reshape(-1)
+    offs, szs, _n = host._list(offsets, sizes)
     # dst's stamp to every rank (dev, ino, size, nlink, mtime, ctime; all -1: none)
     fields = [f for f, _t in FileStamp._fields_]
     st_t = torch.full((len(fields),), -1, dtype=torch.int64, device=where)

@@ -12,9 +12,10 @@ from __future__ import annotations
 
 import ctypes
 import re
-from typing import List, Optional, Tuple
+from typing import List, Tuple
 
-from ._lib import SF_WIRE_END, SF_WIRE_INCOMPLETE, SF_WIRE_MALFORMED, SF_WIRE_OTHER, check, lib  # noqa: F401
+from ._lib import (SF_ENOSPC, SF_OK, SF_WIRE_END, SF_WIRE_INCOMPLETE, SF_WIRE_MALFORMED,  # noqa: F401
+                   SF_WIRE_OTHER, check, lib)
 from .digest import HashDigest
 
 
@@ -150,24 +151,41 @@ class Parser:
         raise ProtocolError("Unknown command")
 
 
+def _device(t, name: str):
+    """torch and .device, imported on first use (``Parser`` and
+    ``write_message`` need neither), once ``t`` is seen to be a contiguous
+    uint8 HBM tensor."""
+    import torch
+
+    from . import device
+    device._require_device(t, name, torch.uint8)
+    return torch, device
+
+
+def _stream(torch, t) -> int:
+    return torch.cuda.current_stream(t.device).cuda_stream
+
+
+def _build_run(torch, name: str, digests, middle: tuple):
+    """A FILE_BLOCK run as a new uint8 HBM tensor: the entry point ``name``
+    called (digests, *middle, out, cap, &need, stream), once without buffers
+    for the need and once to fill.  Call inside ``_on``."""
+    fn, need, s = getattr(lib(), name), ctypes.c_uint64(0), _stream(torch, digests)
+    rc = fn(None, *middle, None, 0, ctypes.byref(need), s)
+    if rc not in (SF_OK, SF_ENOSPC):
+        check(rc, name)
+    out = torch.empty(need.value, dtype=torch.uint8, device=digests.device)
+    if need.value:
+        check(fn(digests.data_ptr(), *middle, out.data_ptr(), out.numel(), ctypes.byref(need), s), name)
+    return out
+
+
 def file_blocks_device(digests, block_size: int, file_len: int, stream=None):
     """FILE_BLOCK messages for every block of a fixed-tiled file, built on the
     device from a uint8[n, 20] HBM digest table -> uint8 HBM tensor."""
-    from .device import _on, _require_device
-    import torch
-    _require_device(digests, "digests", torch.uint8)
-    n = digests.shape[0]
-    need = ctypes.c_uint64(0)
-    with _on(digests.device, stream):
-        s = torch.cuda.current_stream(digests.device).cuda_stream
-        rc = lib().sf_wire_file_blocks_device(None, n, block_size, file_len, None, 0, ctypes.byref(need), s)
-        if rc not in (0, -28):
-            check(rc, "sf_wire_file_blocks_device")
-        out = torch.empty(need.value, dtype=torch.uint8, device=digests.device)
-        if need.value:
-            check(lib().sf_wire_file_blocks_device(digests.data_ptr(), n, block_size, file_len, out.data_ptr(),
-                                                   out.numel(), ctypes.byref(need), s), "sf_wire_file_blocks_device")
-    return out
+    torch, dev = _device(digests, "digests")
+    with dev._on(digests.device, stream):
+        return _build_run(torch, "sf_wire_file_blocks_device", digests, (digests.shape[0], block_size, file_len))
 
 
 def _check_sizes(torch, sizes, digests):
@@ -181,23 +199,12 @@ def blocks_device(digests, sizes, stream=None):
     blocks, each with its own size), built on the device from a uint8[n, 20]
     HBM digest table and an int32/uint32[n] HBM size array (bit pattern taken
     as uint32) -> uint8 HBM tensor (sf_wire_blocks_device)."""
-    from .device import _on, _require_device
-    import torch
-    _require_device(digests, "digests", torch.uint8)
+    torch, dev = _device(digests, "digests")
     n = digests.shape[0]
     _check_sizes(torch, sizes, digests)
-    need = ctypes.c_uint64(0)
-    with _on(digests.device, stream):
+    with dev._on(digests.device, stream):
         sizes = sizes.contiguous()  # on the stream the kernels run on
-        s = torch.cuda.current_stream(digests.device).cuda_stream
-        rc = lib().sf_wire_blocks_device(None, sizes.data_ptr() if n else None, n, None, 0, ctypes.byref(need), s)
-        if rc not in (0, -28):
-            check(rc, "sf_wire_blocks_device")
-        out = torch.empty(need.value, dtype=torch.uint8, device=digests.device)
-        if need.value:
-            check(lib().sf_wire_blocks_device(digests.data_ptr(), sizes.data_ptr(), n, out.data_ptr(), out.numel(),
-                                              ctypes.byref(need), s), "sf_wire_blocks_device")
-    return out
+        return _build_run(torch, "sf_wire_blocks_device", digests, (dev._ptr(sizes, n), n))
 
 
 def parse_blocks_device(run, stream=None):
@@ -211,21 +218,15 @@ def parse_blocks_device(run, stream=None):
     command's complete line: FILE_END, FILE_START, ...) or SF_WIRE_MALFORMED
     (``Parser`` would raise there).  A size above 2^32 - 1 raises SfError
     (SF_ERANGE).  Blocking."""
-    from .device import _on, _require_device
-    import torch
-    _require_device(run, "run", torch.uint8)
+    torch, dev = _device(run, "run")
     if run.dim() != 1:
         raise ValueError("run must be a flat uint8 tensor")
-    nb = run.numel()
-    cap = nb // 34 + 1  # a message is at least 34 bytes
     n, consumed, stop = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_int(0)
-    with _on(run.device, stream):
-        digests = torch.empty((cap, 20), dtype=torch.uint8, device=run.device)
-        sizes = torch.empty(cap, dtype=torch.int32, device=run.device)
-        s = torch.cuda.current_stream(run.device).cuda_stream
-        check(lib().sf_wire_parse_blocks_device(run.data_ptr() if nb else None, nb, digests.data_ptr(),
-                                                sizes.data_ptr(), cap, ctypes.byref(n), ctypes.byref(consumed),
-                                                ctypes.byref(stop), s), "sf_wire_parse_blocks_device")
+    with dev._on(run.device, stream):
+        cap, digests, sizes = dev._receive_outputs(run, False)
+        check(lib().sf_wire_parse_blocks_device(dev._ptr(run), run.numel(), digests.data_ptr(), sizes.data_ptr(), cap,
+                                                ctypes.byref(n), ctypes.byref(consumed), ctypes.byref(stop),
+                                                _stream(torch, run)), "sf_wire_parse_blocks_device")
     return digests[:n.value], sizes[:n.value].view(torch.uint32), consumed.value, stop.value
 
 
@@ -241,19 +242,16 @@ def blocks_to_fd(digests, sizes, fd: int, stream=None) -> int:
     """The explicit list's FILE_BLOCK run written to a file descriptor, built
     on the device in chunks and streamed back (sf_wire_blocks_fd).  Returns
     the bytes written."""
-    from .device import _on, _require_device
-    import torch
-    _require_device(digests, "digests", torch.uint8)  # an HBM table: the kernels read it on its device
+    torch, dev = _device(digests, "digests")  # an HBM table: the kernels read it on its device
     n = digests.shape[0]
     _check_sizes(torch, sizes, digests)
     out = ctypes.c_uint64(0)
     # the library's streams and chunk buffers are the current device's
     # (HostLease keys on hipGetDevice): enter the digests' device
-    with _on(digests.device, stream):
+    with dev._on(digests.device, stream):
         sizes = sizes.contiguous()  # on the stream the chunks are built after
-        s = torch.cuda.current_stream(digests.device).cuda_stream
-        check(lib().sf_wire_blocks_fd(digests.data_ptr() if n else None, sizes.data_ptr() if n else None, n,
-                                      int(fd), ctypes.byref(out), s), "sf_wire_blocks_fd")
+        check(lib().sf_wire_blocks_fd(dev._ptr(digests, n), dev._ptr(sizes, n), n, int(fd), ctypes.byref(out),
+                                      _stream(torch, digests)), "sf_wire_blocks_fd")
     return out.value
 
 
@@ -262,13 +260,10 @@ def file_blocks_to_fd(digests, block_size: int, file_len: int, fd: int, stream=N
     (an SSH pipe or a file): built on the device in chunks, streamed back by
     DMA and written while the next chunk is built (sf_wire_file_blocks_fd).
     Returns the bytes written."""
-    from .device import _on, _require_device
-    import torch
-    _require_device(digests, "digests", torch.uint8)
+    torch, dev = _device(digests, "digests")
     n = digests.shape[0]
     out = ctypes.c_uint64(0)
-    with _on(digests.device, stream):
-        s = torch.cuda.current_stream(digests.device).cuda_stream
-        check(lib().sf_wire_file_blocks_fd(digests.data_ptr() if n else None, n, block_size, file_len, fd,
-                                           ctypes.byref(out), s), "sf_wire_file_blocks_fd")
+    with dev._on(digests.device, stream):
+        check(lib().sf_wire_file_blocks_fd(dev._ptr(digests, n), n, block_size, file_len, fd, ctypes.byref(out),
+                                           _stream(torch, digests)), "sf_wire_file_blocks_fd")
     return out.value

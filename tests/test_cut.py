@@ -11,35 +11,19 @@ run of the same stand-in over the whole file in memory; and a Python chunker
 against a plain Python loop."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import oracle
+from standin import load as load_standin
 from syncfast_amd import SfError, host
-from syncfast_amd._lib import SF_EAGAIN, SF_EINVAL
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SO = os.path.join(ROOT, "examples", "build", "libzpaq_standin.so")
-
-
-class ChunkerOps(ctypes.Structure):
-    _fields_ = [("create", ctypes.CFUNCTYPE(ctypes.c_void_p, ctypes.c_void_p)),
-                ("next", ctypes.CFUNCTYPE(ctypes.c_size_t, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint8),
-                                          ctypes.c_size_t)),
-                ("destroy", ctypes.CFUNCTYPE(None, ctypes.c_void_p)),
-                ("ctx", ctypes.c_void_p)]
+from syncfast_amd._lib import SF_EAGAIN, SF_EINVAL, ChunkerOps
 
 
 @pytest.fixture(scope="module")
 def standin():
-    if not os.path.exists(SO):
-        subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "examples"), "build/libzpaq_standin.so"])
-    lib = ctypes.CDLL(SO)
-    lib.sf_zpaq_standin_ops.restype = ctypes.c_void_p
-    lib.sf_zpaq_standin_ops.argtypes = [ctypes.c_uint, ctypes.c_uint32]
-    lib.sf_zpaq_standin_ops_free.argtypes = [ctypes.c_void_p]
+    lib = load_standin()
     ops = lib.sf_zpaq_standin_ops(13, 32768)  # ZPAQ_BITS, MAX_BLOCK_SIZE (src/index.rs:40-41)
     yield lib, ops
     lib.sf_zpaq_standin_ops_free(ops)

@@ -350,14 +350,8 @@ def test_fds_fuzz(gpu, tmp_path, seed):
 
 
 def _standin_ops():
-    import ctypes
-    so = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "examples", "build",
-                      "libzpaq_standin.so")
-    assert os.path.exists(so), f"{so} not built: run __graft_entry__.build()"
-    lib = ctypes.CDLL(so)
-    lib.sf_zpaq_standin_ops.restype = ctypes.c_void_p
-    lib.sf_zpaq_standin_ops.argtypes = [ctypes.c_uint, ctypes.c_uint32]
-    lib.sf_zpaq_standin_ops_free.argtypes = [ctypes.c_void_p]
+    from standin import load
+    lib = load()
     return lib, lib.sf_zpaq_standin_ops(13, 32768)
 
 

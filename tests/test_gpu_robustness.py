@@ -348,13 +348,10 @@ def test_scratch_pool_under_alternating_calls(gpu, knobs, tmp_path, pool):
     # (both kept their blocks and were right in 480 iterations, the pools
     # that release at every synchronisation wrong in most:
     # scripts/sort_race_stress.py)
-    import ctypes as C
+    from standin import load
     knobs.set("SF_TEST_STREAM_POOL", pool)
     knobs.set("SF_TEST_STREAM_STAGE_MIB", 1)
-    Z = C.CDLL(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "examples", "build",
-                            "libzpaq_standin.so"))
-    Z.sf_zpaq_standin_ops.restype = C.c_void_p
-    Z.sf_zpaq_standin_ops.argtypes = [C.c_uint, C.c_uint32]
+    Z = load()
     ops = Z.sf_zpaq_standin_ops(13, 32768)
     rng = np.random.default_rng(77)
     files = []

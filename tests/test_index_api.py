@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import oracle
+import standin
 from syncfast_amd import _lib
 from syncfast_amd.digest import HashDigest, InvalidHashDigest
 from syncfast_amd.index import BoundaryChunker, FixedChunker, Index, temp_name, untemp_name
@@ -647,20 +648,6 @@ def test_index_path_stream_chunker_property(tmp_path, monkeypatch):
     assert counter[0] >= 10  # the examples ran
 
 
-def _standin_ops_lib():
-    import ctypes
-    import subprocess as _sp
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    so = os.path.join(root, "examples", "build", "libzpaq_standin.so")
-    if not os.path.exists(so):
-        _sp.check_call(["make", "-s", "-C", os.path.join(root, "examples"), "build/libzpaq_standin.so"])
-    lib = ctypes.CDLL(so)
-    lib.sf_zpaq_standin_ops.restype = ctypes.c_void_p
-    lib.sf_zpaq_standin_ops.argtypes = [ctypes.c_uint, ctypes.c_uint32]
-    lib.sf_zpaq_standin_ops_free.argtypes = [ctypes.c_void_p]
-    return lib
-
-
 def test_native_chunker_matches_the_python_chunker(tmp_path, monkeypatch):
     """Index with a NativeChunker (the stand-in's sf_chunker_ops): index_file
     (sf_index_fd_cut: the library cuts on its threads -- really, sf_cut_fd is
@@ -683,7 +670,7 @@ def test_native_chunker_matches_the_python_chunker(tmp_path, monkeypatch):
         return rows, oracle.blocks_hash(dig)
 
     monkeypatch.setattr(host, "index_fd_cut", fd_cut)
-    lib = _standin_ops_lib()
+    lib = standin.load()
     ops = lib.sf_zpaq_standin_ops(13, 32768)
     try:
         root = tmp_path / "tree"
@@ -734,7 +721,7 @@ def test_index_path_large_files_and_fifo_keep_walk_order(tmp_path, monkeypatch):
         return rows, oracle.blocks_hash(dig)
 
     monkeypatch.setattr(host, "index_fd_cut", fd_cut)
-    lib = _standin_ops_lib()
+    lib = standin.load()
     ops = lib.sf_zpaq_standin_ops(13, 32768)
     root = tmp_path / "tree"
     (root / "sub").mkdir(parents=True)
