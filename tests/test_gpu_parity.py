@@ -11,6 +11,7 @@ import pytest
 import torch
 
 import oracle
+from block_paths import TABLE_SORT_MIN, table_waves
 from syncfast_amd import SfError, _lib, device, host
 
 pytestmark = pytest.mark.gpu
@@ -98,16 +99,23 @@ def test_table_unsorted_overlapping_empty_blocks(gpu):
     sizes = rng.integers(0, 40_000, m).astype(np.int64)
     sizes[rng.integers(0, m, 50)] = 0
     offs = np.array([int(rng.integers(0, n - s + 1)) for s in sizes], np.int64)
-    # a few 16-B aligned runs so some waves take the LDS path
+    # two waves' worth of 16-B aligned blocks.  Their sizes differ, so the
+    # slot path takes them like every other wave (hash_wave_list; only aligned
+    # waves of equal sizes still take the LDS tile, test_gpu_block_paths.py),
+    # in list order and in the sorted order this launch of 1000 blocks takes
     offs[:128] = (offs[:128] // 16) * 16
+    assert t.data_ptr() % 16 == 0
+    assert table_waves(0, offs[:128], sizes[:128], n, False, False) == [("slot", None, None)] * 2
+    assert table_waves(0, offs, sizes, n, False, m >= TABLE_SORT_MIN) == [("slot", None, None)] * 16
     d = device.index_device_blocks(t, torch.from_numpy(offs).to(gpu), torch.from_numpy(sizes.astype(np.int32)).to(gpu))
     want = oracle.index_blocks(data, offs, sizes)
     assert np.array_equal(d.cpu().numpy(), want)
 
 
 def test_table_aligned_contiguous_blocks(gpu):
-    # every block 16-B aligned and contiguous: all waves on the LDS path, with
-    # ragged per-lane sizes (mixed full tiles + per-lane tails)
+    # every block 16-B aligned and contiguous, with ragged sizes: aligned
+    # waves whose sizes differ take the slot path (hash_wave_list), not the
+    # LDS tile, whose per-lane tails cost more (sf_kernels.hpp, table_group)
     rng = np.random.default_rng(12)
     sizes = (rng.integers(1, 600, 777) * 16 + rng.integers(0, 16, 777) * (rng.random(777) < 0.3)).astype(np.int64)
     offs = np.zeros_like(sizes)
@@ -115,6 +123,8 @@ def test_table_aligned_contiguous_blocks(gpu):
     n = int(offs[-1] + sizes[-1])
     data = oracle.splitmix_bytes(n, 78)
     t = to_dev(data.tobytes(), gpu)
+    assert t.data_ptr() % 16 == 0
+    assert table_waves(0, offs, sizes, n, False, sizes.size >= TABLE_SORT_MIN) == [("slot", None, None)] * 13
     d = device.index_device_blocks(t, torch.from_numpy(offs).to(gpu), torch.from_numpy(sizes.astype(np.int32)).to(gpu))
     assert np.array_equal(d.cpu().numpy(), oracle.index_blocks(data, offs, sizes))
 
