@@ -113,6 +113,77 @@ def test_block_set_colliding_slots(gpu):
     assert got[0] == 64 and got[1] == -1 and got[8] == 8 and got[-1] == -1
 
 
+def _lookup(gpu, table, present, q):
+    from syncfast_amd.device import BlockSet
+    t = torch.from_numpy(np.ascontiguousarray(table)).to(gpu)
+    with BlockSet(t, torch.from_numpy(present).to(gpu) if present is not None else None) as bset:
+        got = bset.lookup(torch.from_numpy(np.ascontiguousarray(q)).to(gpu)).cpu().numpy()
+    assert np.array_equal(got, oracle.block_lookup(table, present, q))
+    return got
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("before_last", [False, True])
+def test_block_set_probe_wraps_past_the_last_slot(gpu, before_last):
+    """Digests whose bytes 0-7 are all 0xFF have the table's last slot as
+    their home at any capacity, so their cluster goes on from slot 0; with 200
+    more whose home is the slot before it (byte 0 = 0xFE) the cluster starts
+    there.  A query absent from the table, same slot and fingerprint, walks
+    the whole wrapped cluster to the first empty slot."""
+    rng = np.random.default_rng(7)
+
+    def family(n, byte0):
+        d = np.full((n, 20), 0xFF, np.uint8)
+        d[:, 0] = byte0
+        d[:, 8:11] = 0x5A  # one fingerprint
+        d[:, 11:] = rng.integers(0, 256, (n, 9), dtype=np.uint8)
+        d[:, 11] = np.arange(n) & 0xFF
+        d[:, 12] = np.arange(n) >> 8  # distinct
+        return d
+
+    last = family(300, 0xFF)
+    table = np.concatenate([last[:40], last, family(200, 0xFE)] if before_last else [last[:40], last])
+    present = np.ones(table.shape[0], bool)
+    present[:20] = False         # first copies not present: the later copy answers
+    present[40 + 100:40 + 110] = False  # single copies not present: no answer
+    absent = family(50, 0xFF)
+    absent[:, 13] ^= 0x80
+    absent2 = family(50, 0xFE)
+    absent2[:, 14] ^= 0x01
+    q = np.concatenate([table, absent, absent2])
+    assert len({bytes(r) for r in table}) == (500 if before_last else 300)
+    assert not {bytes(r) for r in table} & {bytes(r) for r in np.concatenate([absent, absent2])}
+    got = _lookup(gpu, table, present, q)
+    assert got[0] == 40 and got[20] == 20 and got[40 + 105] == -1 and (got[table.shape[0]:] == -1).all()
+    assert (got[40 + 110:table.shape[0]] == np.arange(40 + 110, table.shape[0])).all()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n_rows", [511, 512, 513, 1024, 1025])
+def test_block_set_capacity_edges(gpu, n_rows):
+    """512 rows fill the smallest table (capacity 1024) to exactly 1/2; 513
+    and 1025 rows are the first at the next capacity."""
+    rng = np.random.default_rng(n_rows)
+    table = rng.integers(0, 256, (n_rows, 20), dtype=np.uint8)
+    q = np.concatenate([table, rng.integers(0, 256, (64, 20), dtype=np.uint8)])
+    got = _lookup(gpu, table, None, q)
+    assert np.array_equal(got[:n_rows], np.arange(n_rows)) and (got[n_rows:] == -1).all()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("first_present", [90_000, None])
+def test_block_set_one_digest_in_every_row(gpu, first_present):
+    """100,000 rows insert one digest into one slot; the smallest present row
+    wins whatever order the lanes arrive in."""
+    table = np.tile(np.arange(20, dtype=np.uint8) * 11, (100_000, 1))
+    present = np.zeros(100_000, bool)
+    if first_present is not None:
+        present[first_present:] = True
+    q = np.concatenate([table[:3], table[:1] ^ 1])
+    got = _lookup(gpu, table, present, q)
+    assert got.tolist() == [first_present if first_present is not None else -1] * 3 + [-1]
+
+
 @pytest.mark.gpu
 def test_block_set_config2_table(gpu):
     # config 2's whole signature table (2^21 digests of the 8 GiB stream) as a

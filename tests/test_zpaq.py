@@ -100,6 +100,43 @@ def test_cut_buffer_equals_the_python_restatement(inputs, bits, max_size):
             assert lib_cuts(data, bits, max_size) == zpaq_cuts(data, bits, max_size), n
 
 
+# every (bits, max_size) pair the device join is tested at (test_gpu_zpaq_join.py)
+JOIN_PARAMS = [(6, 256), (5, 48), (6, 17), (7, 100), (4, 33), (9, 1023), (1, 16), (31, 4096), (13, 1 << 20),
+               (20, 1 << 20), (8, 16)]
+
+
+@pytest.mark.parametrize("bits,max_size", JOIN_PARAMS)
+def test_cut_buffer_equals_the_python_restatement_on_islands(bits, max_size):
+    """The host cutter is the reference of the device join's tests: held
+    against `zpaq_cuts` at each of their parameter pairs, on that file's kind
+    of input (random stretches alternating with periodic ones)."""
+    from zpaq_join import islands
+    data = islands(1024, 20261)
+    assert len(data) >= 20_000
+    if (bits, max_size) in ((13, 1 << 20), (9, 1023)):
+        # long enough to hold a forced cut.  In "1 1 2 2 ..." every byte follows its
+        # predecessor for the other time round, so every step multiplies h by 2 HM:
+        # h is a function of the last 32 bytes, four values in all, none below 2^23.
+        data += b"\x01\x01\x02\x02" * (max_size // 4 + 1025) + data[:4097]
+    want = zpaq_cuts(data, bits, max_size)
+    assert lib_cuts(data, bits, max_size) == want
+    assert sum(s for _o, s in want) == len(data) and all(0 < s <= max_size for _o, s in want)
+    if (bits, max_size) in ((13, 1 << 20), (9, 1023), (31, 4096)):
+        assert any(s == max_size for _o, s in want[:-1])
+
+
+def test_device_cut_parameter_limits_clear_the_count():
+    """sf_cut_device_zpaq at the first values outside its range: SF_EINVAL
+    and *n_blocks = 0, before any device work (test_argument_validation_
+    without_device checks the return codes alone)."""
+    L = syncfast_amd.lib()
+    for bits, max_size in ((13, 15), (13, (1 << 20) + 1), (0, 256), (32, 256)):
+        n = ctypes.c_uint64(77)
+        assert L.sf_cut_device_zpaq(1 << 20, 100, bits, max_size, None, None, 0, ctypes.byref(n), None) == \
+            _lib.SF_EINVAL
+        assert n.value == 0, (bits, max_size)
+
+
 @pytest.fixture(scope="module")
 def text_file(tmp_path_factory):
     data = word_salad(20 << 20, 2)
