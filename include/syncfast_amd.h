@@ -146,7 +146,14 @@ int sf_index_device_batch(const void *d_data, uint64_t len, const sf_file_desc *
  * already hashed into d_digests (n_files files x blocks rows, blocks a
  * multiple of 4): part 0 = whole chains -> d_hashes (20 B per file);
  * part 1 = first half of every chain -> d_state (20 B per file);
- * part 2 = second half, resumed from d_state -> d_hashes. */
+ * part 2 = second half, resumed from d_state -> d_hashes.
+ * The chain kernels read the runs in 16-B pieces and the states and hashes
+ * as 32-bit words: d_digests must be 16-B aligned, d_state and d_hashes 4-B
+ * aligned.  A job with n_files != 0 that breaks one of these rules, has
+ * blocks = 0, not a multiple of 4 or more than 214,748,364 (20 * blocks above
+ * 0xFFFFFFF0), part > 2, no d_digests, no d_state in part 1 or 2, or no
+ * d_hashes in part 0 or 2 is SF_EINVAL, and nothing is launched.  A job with
+ * n_files = 0 is skipped, whatever its other fields hold. */
 typedef struct sf_chain_job {
     const void *d_digests;
     uint32_t n_files;

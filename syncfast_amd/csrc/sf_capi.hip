@@ -217,8 +217,10 @@ int batch_with_hashes(const uint8_t* base, uint64_t flen, uint32_t bs, uint32_t 
   // compressions run faster whole and alone with their helper waves than half
   // beside the blocks (64 x 128 MiB: 11.5 ms that way, 12.4 in halves; 16 x
   // 512 MiB 37.2 against 44.0; 256 x 32 MiB the other way, 4.89 against 4.28).
+  // (the chained entry point refuses a table that is not 16-B aligned and
+  // hashes that are not 4-B aligned: such a batch keeps the route below)
   if (halves && nbf % 64 == 0 && nbf >= 128 && nbf <= 16384 && (reinterpret_cast<uintptr_t>(dig) & 15) == 0 &&
-      nbf * nfiles <= launch_max_blocks()) {
+      (reinterpret_cast<uintptr_t>(fh) & 3) == 0 && nbf * nfiles <= launch_max_blocks()) {
     const uint64_t half = (nbf * 20 / 64) / 2;  // data chunks of part 1 (as the chained launcher cuts them)
     const uint64_t need = ceil_div(half * 64, 20);  // digests part 1 reads
     cut = ceil_div(need, 64) * 64;                  // in whole block waves
@@ -484,9 +486,14 @@ int sf_index_device_batch_chained_cols(const void* d_data, uint32_t n_files, uin
   for (uint32_t k = 0; k < n_jobs; k++) {
     const sf_chain_job& j = jobs[k];
     if (!j.n_files) continue;
-    // each file's digest run must start 16-B aligned (20 * blocks % 16 == 0)
+    // each file's digest run must start 16-B aligned: the table does, and
+    // 20 * blocks % 16 == 0 (both chain kernels read the runs as uint4)
     if (!j.d_digests || j.blocks == 0 || j.blocks % 4 || j.blocks * 20 > 0xFFFFFFF0ull || j.part > 2 ||
         (j.part != 0 && !j.d_state) || (j.part != 1 && !j.d_hashes))
+      return SF_EINVAL;
+    // d_state and d_hashes are read and written as uint32 words
+    if ((reinterpret_cast<uintptr_t>(j.d_digests) & 15) || (reinterpret_cast<uintptr_t>(j.d_state) & 3) ||
+        (reinterpret_cast<uintptr_t>(j.d_hashes) & 3))
       return SF_EINVAL;
     const uint32_t run_len = (uint32_t)(j.blocks * 20), data_ch = run_len / 64, half = data_ch / 2;
     cj[k].runs = static_cast<const uint8_t*>(j.d_digests);

@@ -272,7 +272,12 @@ class BatchStream:
     in two column halves, so the first half of its chains runs beside the
     second half's blocks and only the second half of its chains runs alone.
     A batch's digest table must stay alive until its hashes have been
-    returned."""
+    returned.  The chains read a table in 16-byte pieces: a digest tensor
+    that does not start 16-byte aligned (a view a few bytes into a larger
+    buffer), like a batch whose blocks per file are no multiple of 4, raises
+    SfError(SF_EINVAL) at the launch that would chain it (sf_chain_job in
+    include/syncfast_amd.h; the states and hashes, allocated here, are
+    4-byte aligned as it asks)."""
 
     def __init__(self, n_files: int, file_len: int, block_size: int, stream: Optional[torch.cuda.Stream] = None,
                  split: bool = True):

@@ -160,6 +160,64 @@ def test_chained_cols_validation_without_device():
     assert call(0, 4096 * 128, 4096, 0, 128) == 0  # nothing to hash, no jobs: nothing launched
 
 
+def _job_rc(job, n_jobs=1, null_jobs=False):
+    """sf_index_device_batch_chained_cols with no batch (n_files = 0) and
+    `job` last of n_jobs: a refused job returns before anything launches."""
+    jobs = (_lib.ChainJob * 2)()
+    jobs[n_jobs - 1] = job
+    return syncfast_amd.lib().sf_index_device_batch_chained_cols(None, 0, 64 * 128, 64, 0, 128, None,
+                                                                 None if null_jobs else jobs, n_jobs, None)
+
+
+# made-up device addresses: 16-B aligned, never dereferenced (every job below is refused)
+_TAB, _ST, _FH = 1 << 30, 2 << 30, 3 << 30
+
+
+def _job(part=0, blocks=16, tab=_TAB, st=_ST, fh=_FH, nf=5):
+    return _lib.ChainJob(tab, nf, part, blocks, st, fh)
+
+
+@pytest.mark.parametrize("n_jobs", [1, 2])
+@pytest.mark.parametrize("name,job", [(n, j) for n, j in [
+    ("blocks 0", _job(blocks=0)), ("blocks 1", _job(blocks=1)), ("blocks 2", _job(blocks=2)),
+    ("blocks 3", _job(blocks=3)), ("blocks 5", _job(blocks=5)), ("blocks 6", _job(blocks=6)),
+    ("run over 0xFFFFFFF0 bytes", _job(blocks=214748368)),
+    ("part 3", _job(part=3)),
+    ("no table", _job(tab=None)), ("no table, part 1", _job(part=1, tab=None)),
+    ("part 1 without state", _job(part=1, st=None)), ("part 2 without state", _job(part=2, st=None)),
+    ("part 0 without hashes", _job(part=0, fh=None)), ("part 2 without hashes", _job(part=2, fh=None)),
+    ("table + 4", _job(tab=_TAB + 4)), ("table + 8", _job(tab=_TAB + 8)), ("table + 12", _job(tab=_TAB + 12)),
+    ("table + 1", _job(tab=_TAB + 1)), ("table + 4, part 1", _job(part=1, tab=_TAB + 4)),
+    ("table + 8, part 2", _job(part=2, tab=_TAB + 8)),
+    ("state + 1, part 1", _job(part=1, st=_ST + 1)), ("state + 2, part 1", _job(part=1, st=_ST + 2)),
+    ("state + 1, part 2", _job(part=2, st=_ST + 1)), ("state + 2, part 2", _job(part=2, st=_ST + 2)),
+    ("state + 2, part 0", _job(part=0, st=_ST + 2)),
+    ("hashes + 2", _job(fh=_FH + 2)), ("hashes + 2, part 2", _job(part=2, fh=_FH + 2)),
+    ("hashes + 2, part 1", _job(part=1, fh=_FH + 2)),
+]], ids=lambda v: v.replace(" ", "_").replace(",", "") if isinstance(v, str) else "job")
+def test_chained_cols_refuses_job(name, job, n_jobs):
+    # include/syncfast_amd.h, sf_chain_job: every rule, as the only job and
+    # as the second of two (the first with n_files = 0: skipped)
+    assert _job_rc(job, n_jobs) == _lib.SF_EINVAL, name
+
+
+def test_chained_cols_job_table_and_empty_jobs():
+    assert _job_rc(_job(), n_jobs=1, null_jobs=True) == _lib.SF_EINVAL  # n_jobs = 1, jobs = NULL
+    assert _job_rc(_job(), n_jobs=2, null_jobs=True) == _lib.SF_EINVAL
+    # n_files = 0: the job is skipped whatever else it holds, nothing to launch
+    for job in (_job(nf=0), _job(nf=0, blocks=0), _job(nf=0, blocks=7, part=9, tab=None, st=_ST + 1, fh=_FH + 3),
+                _job(nf=0, tab=_TAB + 1), _job(nf=0, part=2, st=None, fh=None)):
+        assert _job_rc(job, 1) == 0
+        assert _job_rc(job, 2) == 0
+    two = (_lib.ChainJob * 2)(_job(nf=0, blocks=3), _job(nf=0, part=5))
+    assert syncfast_amd.lib().sf_index_device_batch_chained_cols(None, 0, 64 * 128, 64, 0, 128, None, two, 2,
+                                                                 None) == 0
+    # a refused second job is not hidden by a skipped first one
+    two[1] = _job(tab=_TAB + 4)
+    assert syncfast_amd.lib().sf_index_device_batch_chained_cols(None, 0, 64 * 128, 64, 0, 128, None, two, 2,
+                                                                 None) == _lib.SF_EINVAL
+
+
 def test_batch_stream_column_split():
     # BatchStream.push_last's cut: the first half of a chain (part 1) reads
     # digests [0, ceil(64 * half / 20)), rounded up to whole 64-block waves

@@ -58,6 +58,37 @@ def test_stream_rejects_unaligned_runs(gpu):
         st.push(t, torch.empty_like(d))  # its launch would chain the first batch
 
 
+def test_split_falls_back_below_two_data_chunks():
+    # 4 digests per file = 80-B runs, one data chunk: nothing to halve
+    assert device.BatchStream(5, 4 * 64, 64, split=True).split is False
+    assert device.BatchStream(5, 8 * 64, 64, split=True).split is True
+
+
+def test_stream_rejects_unaligned_table(gpu):
+    # a digest table that starts 4 bytes into a buffer: its runs are not 16-B
+    # aligned, the launch that would chain it refuses (sf_chain_job)
+    nf, flen, bs = 4, 64 * 8, 64
+    host, t = _batch(nf, flen, 3, gpu)
+    buf = torch.empty(nf * 8 * 20 + 16, dtype=torch.uint8, device=gpu)
+    d = buf[4:4 + nf * 8 * 20]
+    assert buf.data_ptr() % 16 == 0 and d.data_ptr() % 16 == 4
+    st = device.BatchStream(nf, flen, bs)
+    assert st.push(t, d) is None  # the blocks themselves go to any 4-B aligned table
+    want = oracle.index_fixed(host, bs)[2]
+    assert np.array_equal(d.cpu().numpy().reshape(-1, 20), want)
+    with pytest.raises(SfError) as e:
+        st.push(t, torch.empty((nf * 8, 20), dtype=torch.uint8, device=gpu))
+    assert e.value.code == SF_EINVAL
+    # a fresh stream over an aligned table works
+    st = device.BatchStream(nf, flen, bs)
+    d2 = torch.empty((nf * 8, 20), dtype=torch.uint8, device=gpu)
+    assert st.push(t, d2) is None
+    (h,) = st.finish()
+    assert np.array_equal(d2.cpu().numpy(), want)
+    per_file = want.reshape(nf, -1, 20)
+    assert [bytes(x) for x in h.cpu().numpy()] == [oracle.blocks_hash(per_file[i]) for i in range(nf)]
+
+
 def test_push_last_single_batch(gpu):
     # a stream of one batch: push_last alone runs both halves and the chains
     nf, flen, bs = 33, 4096 * 256, 4096
