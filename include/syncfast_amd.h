@@ -306,6 +306,62 @@ int sf_receive_blocks_buffer(const sf_block_set *set, const void *wire /* host *
                              uint64_t base_offset, sf_block_sig *out, int64_t *src_rows, uint64_t cap,
                              uint64_t *n_out, uint64_t *consumed, int *stop, uint64_t *end_offset);
 
+/* ------------------------------ receiving a BLOCK_DATA run, on the device ---- */
+
+/* The messages that carry the bytes: after GET_BLOCK the source answers with
+ * BLOCK_DATA messages (written by src/sync/ssh/proto.rs:175-181, parsed by
+ * :419-446), and the sink's GetBlocks state writes each payload to every
+ * location that wants it (src/sync/fs.rs:503-516) -- without hashing it
+ * (fs.rs:505-510): a corrupt payload is written and marked present.  This
+ * call parses a received run on the device exactly as the reference parser
+ * reads it and, unlike the reference, checks every payload against the digest
+ * its message claims.
+ *
+ * Message i = "BLOCK_DATA\n" + 20 digest bytes + "\n" + a length field (what
+ * usize::from_str takes, at most 15 bytes) + "\n" + `length` payload bytes +
+ * "\n".  The longest prefix of whole messages of d_wire[0, n_bytes): the
+ * claimed digest of message i goes to d_digests + 20 * i (4-B aligned, the
+ * table sf_block_set_lookup takes), its payload's length to d_sizes[i] and
+ * its payload's offset from d_wire to d_data_offsets[i].  *n_out = the
+ * messages, *consumed = their bytes, *stop = SF_WIRE_* for what stands at
+ * d_wire + *consumed (FILE_BLOCK is one of the other commands here; a wrong
+ * byte after a payload, "Invalid data end byte", is SF_WIRE_MALFORMED).  With
+ * SF_WIRE_INCOMPLETE after a whole header, *need = that message's full length
+ * (the bytes from *consumed on that complete it), else 0.
+ *
+ * With d_ok, every payload is hashed where it lies (the explicit-list kernel
+ * of sf_index_device_blocks over d_wire) and d_ok[i] = 1 when its SHA-1 is the
+ * claimed digest, else 0; *n_bad = the payloads that did not verify.  d_ok
+ * NULL: parse only, nothing is hashed.
+ *
+ * A payload is arbitrary file content and may hold whole BLOCK_DATA messages
+ * of its own, or headers whose length lands on a later message's end byte.
+ * Every byte position is tested for a whole message in parallel; when no such
+ * candidate lies inside a chained message the chain is found on the device,
+ * else only the candidates' positions and lengths (16 B each, no payload
+ * byte) go to the host, which walks them (sf_recv_data.hip).
+ * The result is the reference parser's for any input.
+ *
+ * d_wire needs no alignment.  A chained length above 2^32 - 1 gives
+ * SF_ERANGE.  SF_ENOSPC with *n_out = the need (the first cap entries
+ * written, nothing hashed) when cap is too small or one of d_digests,
+ * d_sizes, d_data_offsets is NULL (a query).  n_bytes == 0 gives 0 messages
+ * and launches nothing; n_bytes <= 2^38.  Blocking. */
+int sf_receive_block_data_device(const void *d_wire, uint64_t n_bytes, void *d_digests /* 4-B aligned */,
+                                 uint32_t *d_sizes, uint64_t *d_data_offsets,
+                                 uint8_t *d_ok /* NULL: parse only */, uint64_t cap,
+                                 uint64_t *n_out, uint64_t *consumed, int *stop, uint64_t *need,
+                                 uint64_t *n_bad, void *stream);
+
+/* The same from host memory: the run goes to HBM through the pinned stages,
+ * out[i] = {offset = the payload's offset in wire, size, sha1 = the claimed
+ * digest} and ok[i] (NULL: parse only) come back; no payload byte does.
+ * SF_ENOSPC with the need when cap is too small or out is NULL.  SF_ENODEV
+ * without a device.  Blocking. */
+int sf_receive_block_data_buffer(const void *wire /* host */, uint64_t n_bytes, sf_block_sig *out, uint8_t *ok,
+                                 uint64_t cap, uint64_t *n_out, uint64_t *consumed, int *stop,
+                                 uint64_t *need, uint64_t *n_bad);
+
 /* Deterministic synthetic input (bench / tests): bytes [start, start+len)
  * of the splitmix64 stream with this seed. */
 int sf_fill_splitmix_device(void *d_out, uint64_t len, uint64_t seed, uint64_t start, void *stream);

@@ -87,6 +87,14 @@ int sf_test_zpaq_device_stats(uint64_t out[4]);
  * out[3] reserved (0).  Host only; not synchronised with calls in flight. */
 int sf_test_wire_parse_stats(uint64_t out[4]);
 
+/* What the last BLOCK_DATA parse of this process did (sf_receive_block_data_device
+ * / _buffer): out[0] the candidate positions the device found, out[1] the
+ * messages, out[2] 1 if the host walked the candidate list (a candidate inside
+ * a chained message, or SF_TEST_BLOCK_DATA_WALK), out[3] the bytes of that list
+ * copied back for it (16 per candidate; never payload bytes).  Host only; not
+ * synchronised with calls in flight. */
+int sf_test_block_data_stats(uint64_t out[4]);
+
 #ifdef __cplusplus
 }
 #endif

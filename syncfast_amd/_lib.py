@@ -117,6 +117,8 @@ def _table():
         "sf_wire_parse_blocks_device": (i32, [vp, u64, vp, vp, u64, pu64, pu64, pint, vp]),
         "sf_receive_blocks_device": (i32, [vp, vp, u64, u64, vp, vp, vp, vp, u64, pu64, pu64, pint, pu64, vp]),
         "sf_receive_blocks_buffer": (i32, [vp, vp, u64, u64, sig, vp, u64, pu64, pu64, pint, pu64]),
+        "sf_receive_block_data_device": (i32, [vp, u64, vp, vp, vp, vp, u64, pu64, pu64, pint, pu64, pu64, vp]),
+        "sf_receive_block_data_buffer": (i32, [vp, u64, sig, vp, u64, pu64, pu64, pint, pu64, pu64]),
         "sf_fill_splitmix_device": (i32, [vp, u64, u64, u64, vp]),
         "sf_index_buffer": (i32, [vp, u64, u32, sig, u64, pu64]),
         "sf_index_buffer_blocks": (i32, [vp, u64, vp, vp, u64, sig, vp]),
@@ -159,6 +161,7 @@ def _table():
         "sf_test_xcd_litmus": (i32, [i32, pu32]),
         "sf_test_zpaq_device_stats": (i32, [vp]),
         "sf_test_wire_parse_stats": (i32, [vp]),
+        "sf_test_block_data_stats": (i32, [vp]),
     }
     return public, test
 

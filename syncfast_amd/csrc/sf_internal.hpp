@@ -13,7 +13,9 @@
 //   sf_zpaq.cpp   the reference's ZPAQ chunker on the host;
 //   sf_cdc.hip    the same boundaries cut on the device (its own kernels);
 //   sf_recv.hip   FILE_BLOCK runs parsed on the device (its own kernels; the
-//                 host parser is sf_wire_parse.hpp).
+//                 host parser is sf_wire_parse.hpp);
+//   sf_recv_data.hip  BLOCK_DATA runs parsed and their payloads verified on
+//                 the device (its own kernels; the rules are sf_wire_data.hpp).
 // The .cpp files use only the HIP runtime API (no kernels), so they build
 // with the host compiler.
 #pragma once
@@ -57,6 +59,7 @@ enum Knob {
   K_BATCH_FUSED,
   K_TEST_INPLACE_FAIL_AT, K_TEST_WIRE_CHUNK, K_TEST_STREAM_STAGE_MIB, K_TEST_LAUNCH_MAX_BLOCKS, K_TEST_TABLE_SORT,
   K_TEST_MULTI_SELF_GATHER, K_TEST_CUT_WINDOW_MIB, K_TEST_STREAM_POOL, K_TEST_ZPAQ_WINDOW, K_TEST_WIRE_PARSE_HOST,
+  K_TEST_BLOCK_DATA_WALK,
   K_COUNT
 };
 struct KnobDef {

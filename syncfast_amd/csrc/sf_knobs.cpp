@@ -36,6 +36,7 @@ const KnobDef kKnobDefs[K_COUNT] = {
     {"SF_TEST_STREAM_POOL", 1},         // K_TEST_STREAM_POOL: scratch pool (1 own, keeps blocks; 0 / 3 known wrong)
     {"SF_TEST_ZPAQ_WINDOW", 0},         // K_TEST_ZPAQ_WINDOW: sf_index_fd_zpaq's window in bytes (0 = 512 MiB)
     {"SF_TEST_WIRE_PARSE_HOST", 0},     // K_TEST_WIRE_PARSE_HOST: 1 = FILE_BLOCK runs are parsed by the host fallback
+    {"SF_TEST_BLOCK_DATA_WALK", 0},     // K_TEST_BLOCK_DATA_WALK: 1 = every BLOCK_DATA run takes the host walk; 2 = and the buffer route parses on the host
 };
 
 std::atomic<int64_t> g_knob[K_COUNT];

@@ -350,6 +350,26 @@ def index_file_multi(path, block_size: int, n_devices: int = 0) -> Tuple[np.ndar
     return out[:n], bytes(bh)
 
 
+def receive_block_data(buf, verify: bool = True):
+    """A received run of BLOCK_DATA messages in host memory, parsed and
+    verified on the device (sf_receive_block_data_buffer) -> (rows, ok,
+    consumed, stop, need): rows[i] = (offset of payload i in ``buf``, its
+    size, the digest its message claims), ok uint8[n] = the payload's SHA-1
+    is that digest (None with ``verify=False``: nothing is hashed), and what
+    stands after the messages (wire.receive_block_data_device).  No payload
+    byte comes back from the device."""
+    a = _u8(buf)
+    cap = a.size // 35 + 1  # a message is at least 35 bytes
+    out, p = _rows(cap)
+    ok = np.zeros(cap, np.uint8) if verify else None
+    n, consumed, stop = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_int(0)
+    need, n_bad = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    check(lib().sf_receive_block_data_buffer(_ptr(a), a.size, p, ok.ctypes.data if verify else None, cap,
+                                             ctypes.byref(n), ctypes.byref(consumed), ctypes.byref(stop),
+                                             ctypes.byref(need), ctypes.byref(n_bad)), "sf_receive_block_data_buffer")
+    return out[:n.value], ok[:n.value] if verify else None, consumed.value, stop.value, need.value
+
+
 def blocks_hash(digests) -> bytes:
     """compute_blocks_hash: SHA-1 over the 20-byte digests in order."""
     d = _u8(digests)

@@ -451,6 +451,62 @@ class Index:
         return [(PurePath(rows[r][2]), int(rows[r][3]), int(o), int(s))
                 for o, s, r in zip(offsets, sizes, found) if r >= 0]
 
+    def apply_block_data(self, digests, sizes, data_offsets, ok=None):
+        """The database half of ``receive_block_data``, from the parsed arrays
+        (no GPU): for each message in order whose payload verified (``ok``
+        None: all of them, as the reference takes them) and for every row of
+        ``list_block_locations(hash)``, ``mark_block_present`` and one entry
+        (name, offset, data_start, size) of the returned write list
+        (src/sync/fs.rs:506-510).  Messages that did not verify come back as
+        ``rejected`` digests: nothing is listed for them and their rows keep
+        present = 0.  Returns (writes, rejected)."""
+        writes, rejected = [], []
+        for i, d in enumerate(digests):
+            h = HashDigest(bytes(d))
+            if ok is not None and not ok[i]:
+                rejected.append(h)
+                continue
+            for file_id, name, offset, _size in self.list_block_locations(h):
+                self.mark_block_present(file_id, h, offset)
+                writes.append((name, offset, int(data_offsets[i]), int(sizes[i])))
+        return writes, rejected
+
+    def receive_block_data(self, data, device=None, verify: bool = True):
+        """The sink's GetBlocks state (src/sync/fs.rs:503-516) for a whole
+        received run of BLOCK_DATA messages in one device call
+        (``wire.receive_block_data_device``): the run is parsed as the
+        reference parser reads it and, with ``verify``, every payload is
+        hashed on the device and compared with the digest it claims -- the
+        check the reference leaves out (fs.rs:505-510).
+
+        Returns (writes, rejected, consumed).  writes: for each verified
+        message in order and each location that wants its block, (name,
+        offset, data_start, size) -- ``data[data_start:data_start + size]``
+        belongs at ``offset`` of file ``name``; the rows are marked present,
+        the bytes are NOT written by this call (file I/O stays out of Index:
+        write them before ``commit()``).  rejected: the digests of messages
+        whose payload did not verify; their rows keep present = 0, so
+        ``list_missing_blocks`` still asks for them.  consumed: the bytes of
+        the whole messages; an incomplete message after them is the caller's
+        to keep for the next call.  Bytes the parser raises on, or another
+        command, right after the messages raise wire.ProtocolError, and
+        nothing is written."""
+        import torch
+
+        from . import wire
+        data = bytes(data)
+        dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        run = torch.frombuffer(bytearray(data), dtype=torch.uint8).to(dev) if data else \
+            torch.empty(0, dtype=torch.uint8, device=dev)
+        digests, sizes, offsets, ok, consumed, stop, _need = wire.receive_block_data_device(run, verify=verify)
+        if stop == wire.SF_WIRE_MALFORMED:
+            raise wire.ProtocolError("Malformed BLOCK_DATA run at byte %d" % consumed)
+        if stop == wire.SF_WIRE_OTHER:
+            raise wire.ProtocolError("Unexpected message in a BLOCK_DATA run (byte %d)" % consumed)
+        writes, rejected = self.apply_block_data(digests.cpu().numpy(), sizes.cpu().numpy(), offsets.cpu().numpy(),
+                                                 ok.cpu().numpy() if verify else None)
+        return writes, rejected, consumed
+
     def get_file(self, name) -> Optional[Tuple[int, DateTimeUtc, Optional[HashDigest]]]:
         row = self.db.execute(
             "SELECT file_id, modified, blocks_hash FROM files WHERE name = ? AND temporary = 0;",

@@ -238,6 +238,49 @@ def parse_stats():
     return tuple(int(v) for v in out)
 
 
+def receive_block_data_device(run, verify: bool = True, stream=None):
+    """A received run of BLOCK_DATA messages, parsed and verified on the
+    device (sf_receive_block_data_device): the messages ``Parser`` reads from
+    byte 0 of ``run``, a uint8 HBM tensor, until something else stands there
+    -> (digests uint8[n, 20] as claimed, sizes uint32[n], data_offsets
+    int64[n] of the payloads in ``run``, ok uint8[n], consumed, stop, need).
+    ``ok[i]`` is 1 when payload i's SHA-1 is the digest its message claims --
+    the check the reference leaves out (src/sync/fs.rs:505-510); with
+    ``verify=False`` nothing is hashed and ``ok`` is None.  ``stop`` is the
+    SF_WIRE_* class of what stands at ``run[consumed:]``; with
+    SF_WIRE_INCOMPLETE after a whole header, ``need`` is that message's full
+    length, else 0.  Payloads may hold messages of their own: the result is
+    the reference parser's for any input.  Blocking."""
+    torch, dev = _device(run, "run")
+    if run.dim() != 1:
+        raise ValueError("run must be a flat uint8 tensor")
+    n, consumed, stop = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_int(0)
+    need, n_bad = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    with dev._on(run.device, stream):
+        cap = run.numel() // 35 + 1  # a message is at least 35 bytes
+        digests = torch.empty((cap, 20), dtype=torch.uint8, device=run.device)
+        sizes = torch.empty(cap, dtype=torch.int32, device=run.device)
+        offsets = torch.empty(cap, dtype=torch.int64, device=run.device)
+        ok = torch.empty(cap, dtype=torch.uint8, device=run.device) if verify else None
+        check(lib().sf_receive_block_data_device(dev._ptr(run), run.numel(), digests.data_ptr(), sizes.data_ptr(),
+                                                 offsets.data_ptr(), dev._ptr(ok), cap, ctypes.byref(n),
+                                                 ctypes.byref(consumed), ctypes.byref(stop), ctypes.byref(need),
+                                                 ctypes.byref(n_bad), _stream(torch, run)),
+              "sf_receive_block_data_device")
+    k = n.value
+    return (digests[:k], sizes[:k].view(torch.uint32), offsets[:k], ok[:k] if verify else None, consumed.value,
+            stop.value, need.value)
+
+
+def block_data_stats():
+    """Test hook (sf_test_block_data_stats): (candidates, messages, 1 if the
+    host walked the candidate list, list bytes copied back for it) of this
+    process's last BLOCK_DATA parse."""
+    out = (ctypes.c_uint64 * 4)()
+    check(lib().sf_test_block_data_stats(out), "sf_test_block_data_stats")
+    return tuple(int(v) for v in out)
+
+
 def blocks_to_fd(digests, sizes, fd: int, stream=None) -> int:
     """The explicit list's FILE_BLOCK run written to a file descriptor, built
     on the device in chunks and streamed back (sf_wire_blocks_fd).  Returns
