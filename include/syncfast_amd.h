@@ -362,6 +362,61 @@ int sf_receive_block_data_buffer(const void *wire /* host */, uint64_t n_bytes, 
                                  uint64_t cap, uint64_t *n_out, uint64_t *consumed, int *stop,
                                  uint64_t *need, uint64_t *n_bad);
 
+/* --------------------------- assembling the incoming files, on the device ---- */
+
+/* What the two sink states exist for: every block the destination already
+ * holds is read from its local file and written into the incoming one
+ * (read_block + write_block, src/sync/fs.rs:463-470), every received payload
+ * is written to each location that wants it (fs.rs:505-510).  Here a whole
+ * copy or write list is carried out in one launch, from HBM to HBM: d_src is
+ * the received run (or a local file's bytes), d_dst the image of the incoming
+ * files.
+ *
+ * dst[d_dst_offsets[i], +d_sizes[i]) = src[d_src_offsets[i], +d_sizes[i]) for
+ * every i in [0, n_blocks) with d_take[i] != 0 (d_take NULL: all) -- the d_ok
+ * of sf_receive_block_data_device goes straight in when jobs and messages are
+ * one to one.  Sizes are any uint32 (0: nothing is written), offsets any
+ * uint64; neither buffer nor any offset needs an alignment.  Source ranges may
+ * overlap or repeat.  The DESTINATION RANGES OF THE TAKEN JOBS MUST BE
+ * DISJOINT: jobs are written concurrently, and where two overlap each byte
+ * there comes from one of them, unspecified which.  Ranges that abut byte to
+ * byte are fine: no store touches a byte outside its own job's range (edges
+ * are byte stores, everything between 16-byte stores aligned in the
+ * destination), and no load leaves [d_src, d_src + src_len).
+ *
+ * A taken job whose source does not lie in [0, src_len) or whose destination
+ * does not lie in [0, dst_len) (offset + size past 2^64 included) is not
+ * copied and *d_status (a device int32 the caller initialised to 0, may be
+ * NULL; the convention of sf_index_device_blocks) is set to SF_ERANGE; every
+ * other job is still copied exactly.
+ *
+ * Work is split by bytes, not jobs (tiles of 4 KiB of the destination, found
+ * through a uint64 scan of per-job tile counts; sf_copy.hip),
+ * the grid is sized from the device's CU count and nothing is read back:
+ * asynchronous on `stream`.  Scratch: 8 (n_blocks + 1) bytes plus the scan's,
+ * from the library's stream-ordered pool; the first call on a device also
+ * allocates 256 bytes of counters that are kept (sf_test_copy_stats reads
+ * them).  n_blocks == 0 launches nothing.
+ * SF_EINVAL, before any device call, for a NULL list or buffer with
+ * n_blocks > 0, for n_blocks > 2^32, and when [d_src, +src_len) and
+ * [d_dst, +dst_len) overlap. */
+int sf_copy_blocks_device(const void *d_src, uint64_t src_len, void *d_dst, uint64_t dst_len,
+                          const uint64_t *d_src_offsets, const uint64_t *d_dst_offsets,
+                          const uint32_t *d_sizes, const uint8_t *d_take /* NULL: all */,
+                          uint64_t n_blocks, int *d_status /* may be NULL */, void *stream);
+
+/* d_data[0, len) written at file_offset of fd with pwrite (the position is
+ * not used or moved): the way of a finished image to its temp file, before
+ * the rename of fs.rs:529-548.  The bytes come back in stages (64 MiB) by DMA
+ * into pinned buffers, after what `stream` holds at the call; stage k is
+ * copied while stage k - 2 is written in slices by the library's reader
+ * threads.  *n_written (may be NULL) = the bytes of the whole stages known
+ * written.  SF_EIO on a failed or short write, SF_EINVAL for fd < 0, a
+ * descriptor that cannot seek (a pipe: pwrite's ESPIPE) or a NULL d_data with
+ * len > 0.  Blocking. */
+int sf_write_device_fd(const void *d_data, uint64_t len, int fd, uint64_t file_offset,
+                       uint64_t *n_written, void *stream);
+
 /* Deterministic synthetic input (bench / tests): bytes [start, start+len)
  * of the splitmix64 stream with this seed. */
 int sf_fill_splitmix_device(void *d_out, uint64_t len, uint64_t seed, uint64_t start, void *stream);

@@ -95,6 +95,15 @@ int sf_test_wire_parse_stats(uint64_t out[4]);
  * synchronised with calls in flight. */
 int sf_test_block_data_stats(uint64_t out[4]);
 
+/* What the last sf_copy_blocks_device of this process did: out[0] T, the tile
+ * size in bytes (also without a call, and without a device), out[1] the jobs
+ * it copied (taken and in range; empty ones count), out[2] their tiles,
+ * out[3] the launches of the copy kernel (0: n_blocks == 0 or an argument
+ * error).  out[1] and out[2] are counted on the device: the call's device is
+ * synchronised to read them.  Not synchronised with calls in flight on other
+ * threads. */
+int sf_test_copy_stats(uint64_t out[4]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -119,6 +119,8 @@ def _table():
         "sf_receive_blocks_buffer": (i32, [vp, vp, u64, u64, sig, vp, u64, pu64, pu64, pint, pu64]),
         "sf_receive_block_data_device": (i32, [vp, u64, vp, vp, vp, vp, u64, pu64, pu64, pint, pu64, pu64, vp]),
         "sf_receive_block_data_buffer": (i32, [vp, u64, sig, vp, u64, pu64, pu64, pint, pu64, pu64]),
+        "sf_copy_blocks_device": (i32, [vp, u64, vp, u64, vp, vp, vp, vp, u64, vp, vp]),
+        "sf_write_device_fd": (i32, [vp, u64, i32, u64, pu64, vp]),
         "sf_fill_splitmix_device": (i32, [vp, u64, u64, u64, vp]),
         "sf_index_buffer": (i32, [vp, u64, u32, sig, u64, pu64]),
         "sf_index_buffer_blocks": (i32, [vp, u64, vp, vp, u64, sig, vp]),
@@ -162,6 +164,7 @@ def _table():
         "sf_test_zpaq_device_stats": (i32, [vp]),
         "sf_test_wire_parse_stats": (i32, [vp]),
         "sf_test_block_data_stats": (i32, [vp]),
+        "sf_test_copy_stats": (i32, [vp]),
     }
     return public, test
 

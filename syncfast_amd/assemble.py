@@ -1,0 +1,236 @@
+"""The incoming files of a sync, assembled in HBM.
+
+The two sink states of the reference end in file writes: read_block +
+write_block for every block the destination already holds
+(src/sync/fs.rs:463-470), write_block for every location of every received
+payload (fs.rs:505-510), then ``finish`` renames the temp files
+(fs.rs:529-548).  ``Index.receive_file_blocks`` and
+``Index.receive_block_data`` return those writes as lists and write nothing.
+``FileImages`` carries the lists out on the device: one HBM image per incoming
+temp file, filled by the block copy kernel (``device.copy_blocks``,
+sf_copy_blocks_device) in one launch per list, checked as a whole against the
+rows the source announced, and written to the temp file's descriptor
+(``device.write_to_fd``).
+"""
+from __future__ import annotations
+
+import hashlib
+from pathlib import Path
+from typing import Callable, Dict, List, Mapping, Optional
+
+import numpy as np
+import torch
+
+from . import device as _device
+from .index import _name_str
+
+__all__ = ["FileImages"]
+
+
+def _upload(data: bytes, dev: torch.device) -> torch.Tensor:
+    if not data:
+        return torch.empty(0, dtype=torch.uint8, device=dev)
+    return torch.frombuffer(bytearray(data), dtype=torch.uint8).to(dev)
+
+
+def _rounds(jobs: List[tuple]) -> List[List[tuple]]:
+    """jobs = [(src_offset, dst_offset, size > 0)] in the order the reference
+    would write them, split into calls of disjoint destinations: a job that
+    overlaps an earlier one goes to a later call than that one.  The usual
+    list overlaps nowhere and is one call, found by a sort; only the jobs that
+    overlap anything are compared pair by pair."""
+    if not jobs:
+        return []
+    involved = [False] * len(jobs)
+    end, holder = -1, -1  # the furthest end among the jobs before, by start, and whose it is
+    for i in sorted(range(len(jobs)), key=lambda i: jobs[i][1]):
+        _s, at, size = jobs[i]
+        if at < end:
+            involved[i] = involved[holder] = True
+        if at + size > end:
+            end, holder = at + size, i
+    rounds: List[List[tuple]] = [[j for i, j in enumerate(jobs) if not involved[i]]]
+    placed: List[tuple] = []  # (dst_offset, end, round) of the involved jobs so far, in list order
+    for i, (s, at, size) in enumerate(jobs):
+        if not involved[i]:
+            continue
+        r = 1 + max((p[2] for p in placed if p[0] < at + size and at < p[1]), default=-1)
+        placed.append((at, at + size, r))
+        while len(rounds) <= r:
+            rounds.append([])
+        rounds[r].append((s, at, size))
+    return [r for r in rounds if r]
+
+
+class FileImages:
+    """One HBM allocation that holds the image of every incoming temp file.
+
+    ``sizes`` maps each temp file's name -- as the write lists spell it, e.g.
+    ``temp_name("a.bin")`` -- to the size FILE_END fixed for it.  An image has
+    exactly that size: it starts zero-filled at a 256-byte-aligned base of the
+    allocation, so one ``copy_blocks`` call serves all files at once, and it
+    never grows.
+    """
+
+    ALIGN = 256
+
+    def __init__(self, sizes: Mapping, device=None, root=None):
+        self.device = torch.device(device) if device is not None else \
+            torch.device("cuda", torch.cuda.current_device())
+        self.root = Path(root) if root is not None else None
+        self._base: Dict[str, int] = {}
+        self._size: Dict[str, int] = {}
+        at = 0
+        for name, size in sizes.items():
+            size = int(size)
+            if size < 0:
+                raise ValueError(f"negative size for {name}")
+            self._base[_name_str(name)] = at
+            self._size[_name_str(name)] = size
+            at += (size + self.ALIGN - 1) // self.ALIGN * self.ALIGN
+        self.buffer = torch.zeros(max(at, 1), dtype=torch.uint8, device=self.device)
+        self._local: Dict[str, torch.Tensor] = {}
+        self._copied: Dict[str, set] = {}  # per image: the offsets apply_copies filled (present at FILE_END)
+
+    def image(self, name) -> torch.Tensor:
+        """The image of temp file ``name``: a view of the allocation."""
+        key = _name_str(name)
+        return self.buffer[self._base[key]: self._base[key] + self._size[key]]
+
+    def _place(self, name, offset: int, size: int) -> int:
+        """Where [offset, offset + size) of ``name`` lies in the allocation."""
+        key = _name_str(name)
+        if key not in self._base:
+            raise KeyError(f"no image for {key}")
+        if offset < 0 or size < 0 or offset + size > self._size[key]:
+            raise ValueError(f"bytes [{offset}, {offset + size}) end past the {self._size[key]} bytes of {key}")
+        return self._base[key] + offset
+
+    def _copy(self, src: torch.Tensor, jobs: List[tuple], stream) -> None:
+        """jobs = [(src_offset, dst_offset in the allocation, size)]."""
+        if not jobs:
+            return
+        a = np.asarray(jobs, dtype=np.int64).reshape(-1, 3)
+        so = torch.from_numpy(a[:, 0].copy()).to(self.device)
+        do = torch.from_numpy(a[:, 1].copy()).to(self.device)
+        sz = torch.from_numpy(a[:, 2].astype(np.uint32).view(np.int32)).to(self.device)
+        _device.copy_blocks(src, self.buffer, so, do, sz, stream=stream)
+
+    def apply_writes(self, writes, data, stream: Optional[torch.cuda.Stream] = None) -> int:
+        """Carry out the write list ``Index.receive_block_data`` returned:
+        ``data[data_start : data_start + size]`` goes to ``offset`` of ``name``
+        for every (name, offset, data_start, size).  ``data`` is the same run,
+        as an HBM tensor or as bytes -- bytes are uploaded here, once, although
+        ``receive_block_data`` uploaded them before: the Python mirror accepts
+        the second upload, the C-ABI path keeps one run in HBM.
+
+        The reference writes in message order, so where two writes cover the
+        same bytes the later one stays.  Exact duplicates of (name, offset,
+        size) keep the last one; the rest is sorted on the host, and writes that
+        still overlap an earlier one of the same call (only possible with
+        ``verify=False``: a payload longer than its row) are put off to a
+        further stream-ordered call, in list order, so the later one wins here
+        too.  A write that ends past its file's size raises ValueError before
+        anything is launched -- the reference would grow the file; an image
+        has the size FILE_END fixed.  Returns the number of copy calls."""
+        src = data if isinstance(data, torch.Tensor) else _upload(bytes(data), self.device)
+        last: Dict[tuple, tuple] = {}
+        for name, offset, start, size in writes:
+            offset, start, size = int(offset), int(start), int(size)
+            at = self._place(name, offset, size)
+            if start < 0 or start + size > src.numel():
+                raise ValueError(f"bytes [{start}, {start + size}) lie outside the run")
+            key = (_name_str(name), offset, size)
+            last.pop(key, None)  # the later one covers it whole, and keeps its own place in the order
+            last[key] = (start, at, size)
+        rounds = _rounds([j for j in last.values() if j[2]])
+        for jobs in rounds:
+            self._copy(src, jobs, stream)
+        return len(rounds)
+
+    def _read_local(self, from_name) -> torch.Tensor:
+        key = _name_str(from_name)
+        if key not in self._local:
+            if self.root is None:
+                raise ValueError("no root to read local files from: pass root= or source=")
+            self._local[key] = _upload(np.fromfile(self.root / key, dtype=np.uint8).tobytes(), self.device)
+        return self._local[key]
+
+    def apply_copies(self, name, copies, source: Optional[Callable] = None,
+                     stream: Optional[torch.cuda.Stream] = None) -> int:
+        """Carry out the copy list ``Index.receive_file_blocks`` returned for
+        temp file ``name``: [(from_name, from_offset, to_offset, size)], the
+        blocks the destination already holds.  ``source(from_name)`` returns
+        an HBM tensor of that local file; the default reads ``root /
+        from_name`` with numpy and uploads it, cached per name -- plumbing, not
+        a fast path (a loader for local files is not part of the library).
+        One copy call per source file.  A copy that ends past the image raises
+        ValueError before anything is launched.  Returns the number of
+        calls."""
+        source = source or self._read_local
+        per: Dict[str, List[tuple]] = {}
+        placed: List[int] = []
+        for from_name, from_offset, to_offset, size in copies:
+            at = self._place(name, int(to_offset), int(size))
+            placed.append(int(to_offset))
+            if int(size):
+                per.setdefault(_name_str(from_name), []).append((int(from_offset), at, int(size)))
+        for from_name, jobs in per.items():
+            self._copy(source(from_name), jobs, stream)
+        self._copied.setdefault(_name_str(name), set()).update(placed)
+        return len(per)
+
+    def check(self, index, name) -> List[int]:
+        """Is the image the file the source announced?  The rows ``index``
+        holds for temp file ``name`` (``list_file_blocks``) are hashed again
+        over the image by the explicit-list kernel (``index_device_blocks``);
+        returns the offsets of the rows whose digest differs, in row order.
+        An empty list means every block is what its row says.  Then SHA-1 of
+        the image's concatenated digests is also compared with
+        ``files.blocks_hash`` where the index has one, and a difference raises
+        ValueError.  That hash was chained at FILE_END over the rows as the
+        index's query returned them then -- through the (file_id, present)
+        index of the reference's schema: the blocks still missing first, then
+        the ones found locally, each group in file order -- so the digests are
+        chained in that order (the local ones are those ``apply_copies`` was
+        given), and in plain file order and the query's present order as well;
+        one of them must give the hash.  The reference never makes this check:
+        it trusts every payload."""
+        key = _name_str(name)
+        row = index.db.execute("SELECT file_id, blocks_hash FROM files WHERE name = ?;", (key,)).fetchone()
+        if not row:
+            raise KeyError(f"the index has no file {key}")
+        rows = index.list_file_blocks(int(row[0]))
+        img = self.image(name)
+        if not rows:
+            return []
+        for _h, offset, size in rows:
+            if offset + size > img.numel():
+                raise ValueError(f"row [{offset}, {offset + size}) ends past the {img.numel()} bytes of {key}")
+        offsets = torch.tensor([r[1] for r in rows], dtype=torch.int64, device=self.device)
+        sizes = torch.tensor([r[2] for r in rows], dtype=torch.int32, device=self.device)
+        if img.numel():
+            got = _device.index_device_blocks(img, offsets, sizes).cpu().numpy()
+        else:  # rows of no bytes in a file of none
+            got = np.tile(np.frombuffer(hashlib.sha1(b"").digest(), np.uint8), (len(rows), 1))
+        empty = np.frombuffer(hashlib.sha1(b"").digest(), np.uint8)
+        bad = []
+        for k, (h, offset, size) in enumerate(rows):
+            d = empty if size == 0 else got[k]
+            if bytes(d) != h.bytes:
+                bad.append(offset)
+        if not bad and row[1] is not None:
+            by_offset = sorted(range(len(rows)), key=lambda k: rows[k][1])
+            local = self._copied.get(key, set())
+            orders = ([k for k in by_offset if rows[k][1] not in local] + [k for k in by_offset if rows[k][1] in local],
+                      by_offset, range(len(rows)))
+            chained = {hashlib.sha1(b"".join(bytes(empty if rows[k][2] == 0 else got[k]) for k in order)).hexdigest()
+                       for order in orders}
+            if str(row[1]) not in chained:
+                raise ValueError(f"blocks_hash of {key} is not that of the image's blocks")
+        return bad
+
+    def write(self, name, fd: int, stream: Optional[torch.cuda.Stream] = None) -> int:
+        """The image of ``name`` written from byte 0 of the open file ``fd``
+        (``device.write_to_fd``); returns the bytes written."""
+        return _device.write_to_fd(self.image(name), fd, 0, stream=stream)

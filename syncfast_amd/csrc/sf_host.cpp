@@ -492,6 +492,61 @@ static int sf_wire_blocks_fd_body(const void* d_digests, const uint32_t* d_sizes
   return rc;
 }
 
+// d_data[0, len) to bytes [file_offset, + len) of fd: stage k comes back by
+// DMA into its pinned buffer while stage k-2 is written with pwrite, in slices
+// on the pool threads (one thread does not keep up with the link).  Stages are
+// 64 MiB (SF_TEST_STREAM_STAGE_MIB: a test's small ones); *n_written counts
+// whole stages known written.
+static int sf_write_device_fd_body(const void* d_data, uint64_t len, int fd, uint64_t file_offset, uint64_t* n_written,
+                                   void* stream) {
+  if (n_written) *n_written = 0;
+  if (fd < 0) return SF_EINVAL;
+  if (lseek(fd, 0, SEEK_CUR) == (off_t)-1 && errno == ESPIPE) return SF_EINVAL;  // pwrite would refuse it too
+  if (len == 0) return SF_OK;
+  if (!d_data) return SF_EINVAL;
+  const int64_t sm = knob(K_TEST_STREAM_STAGE_MIB);
+  const uint64_t stage = std::min<uint64_t>(len, sm > 0 ? (uint64_t)sm << 20 : (64ull << 20));
+  const uint64_t nstages = ceil_div(len, stage);
+  HostLease res;
+  hipStream_t* st;
+  hipEvent_t* ev;
+  void* pin[2] = {nullptr, nullptr};
+  hipEvent_t ready = nullptr;
+  int rc = res.streams(st, ev);
+  for (int i = 0; i < 2 && rc == SF_OK; i++) rc = res.pin(kSlotData + i, stage, &pin[i]);
+  if (rc != SF_OK) return rc;
+  SF_HIP(hipEventCreateWithFlags(&ready, hipEventDisableTiming));
+  if (hipEventRecord(ready, as_stream(stream)) != hipSuccess ||  // the bytes are produced on the caller's stream
+      hipStreamWaitEvent(st[0], ready, 0) != hipSuccess || hipStreamWaitEvent(st[1], ready, 0) != hipSuccess)
+    rc = SF_ENODEV;
+  uint64_t written = 0;
+  if (rc == SF_OK)
+    rc = two_stage(
+        nstages,
+        [&](uint64_t k, int b) {
+          const uint64_t o = k * stage, m = std::min(stage, len - o);
+          if (hipMemcpyAsync(pin[b], static_cast<const uint8_t*>(d_data) + o, m, hipMemcpyDeviceToHost, st[b]) !=
+                  hipSuccess ||
+              hipEventRecord(ev[b], st[b]) != hipSuccess)
+            return SF_ENODEV;
+          return SF_OK;
+        },
+        [&](uint64_t k, int b) {
+          if (hipEventSynchronize(ev[b]) != hipSuccess) return SF_ENODEV;
+          const uint64_t o = k * stage, m = std::min(stage, len - o);
+          const uint8_t* p = static_cast<const uint8_t*>(pin[b]);
+          const int r = sliced(m, [&](uint64_t a, uint64_t e) {
+            return write_fully(fd, p + a, file_offset + o + a, e - a) ? SF_OK : SF_EIO;
+          });
+          if (r == SF_OK) written += m;
+          return r;
+        });
+  for (int i = 0; i < 2; i++) (void)hipStreamSynchronize(st[i]);
+  (void)hipEventDestroy(ready);
+  if (n_written) *n_written = written;
+  return rc;
+}
+
 }  // extern "C"
 
 namespace {
@@ -1055,6 +1110,11 @@ int sf_wire_blocks_fd(const void* d_digests, const uint32_t* d_sizes, uint64_t n
 int sf_wire_file_blocks_fd(const void* d_digests, uint64_t n_blocks, uint32_t block_size, uint64_t file_len, int fd,
                            uint64_t* n_written, void* stream) {
   return guarded([&] { return sf_wire_file_blocks_fd_body(d_digests, n_blocks, block_size, file_len, fd, n_written, stream); });
+}
+
+int sf_write_device_fd(const void* d_data, uint64_t len, int fd, uint64_t file_offset, uint64_t* n_written,
+                       void* stream) {
+  return guarded([&] { return sf_write_device_fd_body(d_data, len, fd, file_offset, n_written, stream); });
 }
 
 int sf_index_buffer(const uint8_t* data, uint64_t len, uint32_t block_size, sf_block_sig* out, uint64_t cap,

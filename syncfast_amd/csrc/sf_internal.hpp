@@ -16,6 +16,8 @@
 //                 host parser is sf_wire_parse.hpp);
 //   sf_recv_data.hip  BLOCK_DATA runs parsed and their payloads verified on
 //                 the device (its own kernels; the rules are sf_wire_data.hpp).
+//   sf_copy.hip   the block copy kernel that assembles the incoming files in
+//                 HBM (its own kernels; the arithmetic is sf_copy_plan.hpp).
 // The .cpp files use only the HIP runtime API (no kernels), so they build
 // with the host compiler.
 #pragma once

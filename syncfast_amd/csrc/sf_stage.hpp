@@ -72,6 +72,19 @@ inline bool read_fully(int fd, uint8_t* dst, uint64_t pos, uint64_t want) {
   return true;
 }
 
+// read_fully's write twin: src[0, want) to bytes [pos, pos + want) of fd
+// (pwrite: the position is not used or moved), EINTR tried again.  false: an
+// error, or a write that made no progress.
+inline bool write_fully(int fd, const uint8_t* src, uint64_t pos, uint64_t want) {
+  for (uint64_t put = 0; put < want;) {
+    const ssize_t w = pwrite(fd, src + put, want - put, (off_t)(pos + put));
+    if (w < 0 && errno == EINTR) continue;
+    if (w <= 0) return false;
+    put += (uint64_t)w;
+  }
+  return true;
+}
+
 // fn(a, e) -> SF_ code over [0, n) in slices of at least 4 MiB, about one per
 // thread (one thread moves 10-16 GB/s from the page cache, below the PCIe link
 // the stage is waiting for).  `run(nworkers, worker)` starts the workers,

@@ -32,6 +32,7 @@ __all__ = [
     "index_device_weak", "index_device_blocks_weak", "BatchStream",
     "fill_splitmix", "splitmix_tensor", "BlockSet", "index_device_multi",
     "cut_device_zpaq", "index_device_zpaq", "zpaq_segment_len", "zpaq_device_stats",
+    "copy_blocks", "copy_stats", "write_to_fd",
 ]
 
 
@@ -533,6 +534,17 @@ def index_device_multi(shards: Sequence[torch.Tensor], file_len: int, block_size
     if own_scratch:
         scratch = [torch.empty((max(num_blocks(t.numel(), block_size), 1), 20), dtype=torch.uint8, device=t.device)
                    for t in shards]
+    # A table or scratch allocated here comes from the current stream's pool:
+    # what that stream still has queued on the block's earlier life (a fill of
+    # the tensor that held it before) must land before the library's streams
+    # write it, or it lands on top of the digests.
+    if own_scratch:
+        for r in range(n):
+            for st in {hs[r], gs[r]}:
+                st.wait_stream(torch.cuda.current_stream(shards[r].device))
+    if own_table:
+        for st in {hs[root], gs[root]}:
+            st.wait_stream(torch.cuda.current_stream(dev_root))
     ptr = lambda ts: (ctypes.c_void_p * n)(*[t.data_ptr() for t in ts])  # noqa: E731
     sp = (ctypes.c_void_p * n)(*[s.cuda_stream for s in hs])
     gp = (ctypes.c_void_p * n)(*[s.cuda_stream for s in gs])
@@ -546,6 +558,73 @@ def index_device_multi(shards: Sequence[torch.Tensor], file_len: int, block_size
         for st in {hs[root], gs[root]}:
             table.record_stream(st)
     return table[:nb]
+
+
+def copy_stats() -> Tuple[int, int, int, int]:
+    """(T, jobs copied, tiles, launches) of this process's last copy_blocks
+    (sf_test_copy_stats); synchronises that call's device."""
+    out = (ctypes.c_uint64 * 4)()
+    check(lib().sf_test_copy_stats(out), "sf_test_copy_stats")
+    return tuple(int(v) for v in out)
+
+
+def copy_blocks(src: torch.Tensor, dst: torch.Tensor, src_offsets: torch.Tensor, dst_offsets: torch.Tensor,
+                sizes: torch.Tensor, take: Optional[torch.Tensor] = None, check_range: bool = True,
+                stream: Optional[torch.cuda.Stream] = None) -> None:
+    """dst[dst_offsets[i] : + sizes[i]] = src[src_offsets[i] : + sizes[i]] for
+    every i (with ``take``, uint8 or bool: every i where it is not 0), in one
+    launch of the block copy kernel (sf_copy_blocks_device).
+
+    ``src`` and ``dst`` are uint8 HBM tensors that do not overlap; the lists
+    are int64 / int64 / int32 tensors on the same device, as
+    index_device_blocks takes them (a size is read as uint32).  Nothing needs
+    an alignment; source ranges may overlap or repeat.  The destination ranges
+    of the taken jobs must be disjoint -- where two overlap, each byte comes
+    from one of them, unspecified which; ranges that abut are fine.  A job
+    outside either tensor is not copied; with ``check_range`` it raises
+    SfError(SF_ERANGE) after the stream is synchronised (the other jobs are
+    copied all the same).  Without it the call is asynchronous."""
+    _require_device(src, "src", torch.uint8)
+    _require_device(dst, "dst", torch.uint8, src.device)
+    _require_device(src_offsets, "src_offsets", torch.int64, src.device)
+    _require_device(dst_offsets, "dst_offsets", torch.int64, src.device)
+    _require_device(sizes, "sizes", torch.int32, src.device)
+    n = sizes.numel()
+    if src_offsets.numel() != n or dst_offsets.numel() != n:
+        raise ValueError("src_offsets, dst_offsets and sizes differ in length")
+    if take is not None:
+        if take.dtype == torch.bool:
+            take = take.view(torch.uint8)
+        _require_device(take, "take", torch.uint8, src.device)
+        if take.numel() != n:
+            raise ValueError("take must hold one flag per job")
+    with _on(src.device, stream):
+        status = torch.zeros(1, dtype=torch.int32, device=src.device) if check_range and n else None
+        check(lib().sf_copy_blocks_device(_ptr(src), src.numel(), _ptr(dst), dst.numel(), _ptr(src_offsets),
+                                          _ptr(dst_offsets), _ptr(sizes), _ptr(take), n, _ptr(status),
+                                          _stream_ptr(src, stream)), "sf_copy_blocks_device")
+        if status is not None and int(status.item()) != 0:
+            raise SfError(SF_ERANGE, "sf_copy_blocks_device")
+
+
+def write_to_fd(t: torch.Tensor, fd: int, offset: int = 0, stream: Optional[torch.cuda.Stream] = None) -> int:
+    """The bytes of a uint8 HBM tensor written at ``offset`` of the open file
+    ``fd`` with pwrite -- the descriptor's position is not used or moved
+    (sf_write_device_fd: pinned stages, written by the library's threads while
+    the next stage comes back).  The copy starts after what ``stream`` holds at
+    the call.  Returns the bytes written; a failed or short write raises
+    SfError(SF_EIO) whose ``written`` attribute holds the whole stages known
+    written, a descriptor that cannot seek SfError(SF_EINVAL).  Blocking."""
+    _require_device(t, "t", torch.uint8)
+    nw = ctypes.c_uint64(0)
+    with _on(t.device, stream):
+        rc = lib().sf_write_device_fd(_ptr(t), t.numel(), int(fd), int(offset), ctypes.byref(nw),
+                                      _stream_ptr(t, stream))
+    if rc != 0:
+        err = SfError(rc, "sf_write_device_fd")
+        err.written = nw.value
+        raise err
+    return nw.value
 
 
 def fill_splitmix(out: torch.Tensor, seed: int, start: int = 0,
