@@ -329,8 +329,6 @@ inline uint64_t gcd64(uint64_t a, uint64_t b) {
   return a;
 }
 
-inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 }  // namespace
 
 namespace sfi {

@@ -165,20 +165,11 @@ std::atomic<int> g_copy_dev{-1};  // the device of the last call that launched
 std::atomic<void*> g_dev_stats[sfi::kMaxDevices];
 std::atomic<int> g_cus[sfi::kMaxDevices];
 
-inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 }  // namespace
 
 using namespace sfi;
 
 namespace {
-
-struct Scratch {
-  void* p = nullptr;
-  hipStream_t s;
-  explicit Scratch(hipStream_t s_) : s(s_) {}
-  ~Scratch() { stream_free(p, s); }
-};
 
 // This device's CU count and its DevStats (allocated once, never freed: the
 // runtime may be gone when a static destructor runs).

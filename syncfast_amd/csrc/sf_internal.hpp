@@ -15,7 +15,8 @@
 //   sf_recv.hip   FILE_BLOCK runs parsed on the device (its own kernels; the
 //                 host parser is sf_wire_parse.hpp);
 //   sf_recv_data.hip  BLOCK_DATA runs parsed and their payloads verified on
-//                 the device (its own kernels; the rules are sf_wire_data.hpp).
+//                 the device (its own kernels; the rules are sf_wire_data.hpp;
+//                 what the two parsers share is sf_recv_scan.hpp).
 //   sf_copy.hip   the block copy kernel that assembles the incoming files in
 //                 HBM (its own kernels; the arithmetic is sf_copy_plan.hpp).
 // The .cpp files use only the HIP runtime API (no kernels), so they build
@@ -137,6 +138,17 @@ int launch_table(const void* d_data, uint64_t len, const uint64_t* d_offsets, co
 // reused on the freeing stream only.  stream_alloc returns an SF_ code.
 int stream_alloc(void** p, size_t bytes, hipStream_t s);
 void stream_free(void* p, hipStream_t s);
+// Such scratch, given back on every path out of a call.
+struct Scratch {
+  void* p = nullptr;
+  hipStream_t s;
+  explicit Scratch(hipStream_t s_) : s(s_) {}
+  ~Scratch() { stream_free(p, s); }
+  Scratch(const Scratch&) = delete;
+  Scratch& operator=(const Scratch&) = delete;
+};
+// The parts of one allocation start on 256-byte boundaries.
+inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 int launch_wire(const uint8_t* d_digests, uint64_t n, uint32_t bs, uint32_t last, uint8_t* d_out,
                 hipStream_t stream);
 // FILE_BLOCK runs of explicit lists (sf_wire.hip): end offsets of every

@@ -9,13 +9,9 @@
 // that happens to hold the same bytes: message i starts where message i - 1
 // ends, which is serial.  What is parallel:
 //
-//   candidates  every byte position p is tested (a lane takes 16 of them): p
-//               is a candidate when a whole, valid message stands there
-//               (block_message, the same function the host parser uses).
-//               Every true message start is one; a digest may forge others.
-//               64 positions' flags are one word of a bitmap and one count.
-//   scan        rocprim inclusive scan of the counts: the candidates before
-//               each word, i.e. every candidate's index in position order.
+//   candidates, scan   sf_recv_scan.hpp, shared with sf_recv_data.hip: the
+//               bitmap of every position where block_message holds, and every
+//               candidate's index in position order.
 //   chain       one lane per word, for each of its candidates at p with
 //               length L: the link is good when p + L is a candidate and no
 //               candidate lies in (p, p + L).  The first candidate whose link
@@ -37,22 +33,21 @@
 // waits for another; every loop is bounded by a message's 48 bytes or a
 // word's 64 bits.
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 #include <string.h>
 
 #include <memory>
 
-#include <rocprim/device/device_scan.hpp>
 #include <rocprim/iterator/transform_iterator.hpp>
 
-#include "sf_internal.hpp"
-#include "sf_stage.hpp"
+#include "sf_recv_scan.hpp"
 #include "sf_wire_parse.hpp"
 #include "../../include/syncfast_amd_test.h"
 
-namespace {
+using namespace sfrs;
 
-constexpr uint64_t kMaxRun = 1ull << 38;  // bytes per call: every grid stays far below 2^31 workgroups
+namespace {
 
 // What the host reads back, in one copy.
 struct Result {
@@ -60,65 +55,17 @@ struct Result {
   unsigned long long cand, msgs, end;
   uint32_t too_large, pad;
 };
+static_assert(offsetof(Result, first_bad) == 0 && sizeof(Result::first_bad) == 8 && sizeof(Result) <= 256,
+              "sfrs::Scan::result: 256 bytes that begin with first_bad");
 
-constexpr uint32_t kPerLane = 16;  // byte positions per lane of the candidates kernel
-
-// 0x80 in exactly the bytes of v that equal c
-__device__ __forceinline__ uint32_t bytes_equal(uint32_t v, uint32_t c) {
-  const uint32_t x = v ^ (c * 0x01010101u);
-  return ~(((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x | 0x7F7F7F7Fu);
-}
-
-// One lane per 16 byte positions [p0, p0 + 16): their bytes come as aligned
-// dwords (data itself needs no alignment: the five dwords that hold them are
-// shifted into place) where all five lie inside [data, data + n), else byte by
-// byte, so nothing outside the run is read.  Only a position that holds 'F'
-// is looked at further.  Four lanes' flags make one word of the bitmap.
-__global__ void __launch_bounds__(256) recv_candidates_kernel(const uint8_t* __restrict__ data, uint64_t n,
-                                                              unsigned long long* __restrict__ words,
-                                                              uint32_t* __restrict__ counts) {
-  const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const uint64_t p0 = g * kPerLane;
-  uint32_t w[4] = {0, 0, 0, 0}, mask = 0;
-  if (p0 < n) {
-    const uint32_t a = (uint32_t)(reinterpret_cast<uintptr_t>(data) & 3u);  // the same for every lane: p0 is a multiple of 16
-    if (p0 >= a && p0 - a + kPerLane + 4 <= n) {
-      const uint32_t* q = reinterpret_cast<const uint32_t*>(data + p0 - a);
-      const uint32_t d[5] = {q[0], q[1], q[2], q[3], a ? q[4] : 0u};
-#pragma unroll
-      for (int j = 0; j < 4; j++) w[j] = __funnelshift_r(d[j], d[j + 1], 8 * a);
-    } else {
-      const uint32_t m = n - p0 < kPerLane ? (uint32_t)(n - p0) : kPerLane;
-      for (uint32_t k = 0; k < m; k++) w[k >> 2] |= (uint32_t)data[p0 + k] << (8 * (k & 3));
-    }
-    // the positions that hold 'F', one after the other: most lanes have one
-    // (a message is about 37 bytes), so the wave tests one position at a time
-    unsigned long long f0 = bytes_equal(w[0], 'F') | (unsigned long long)bytes_equal(w[1], 'F') << 32;
-    unsigned long long f1 = bytes_equal(w[2], 'F') | (unsigned long long)bytes_equal(w[3], 'F') << 32;
-    while (f0 | f1) {
-      uint32_t k;
-      if (f0) {
-        k = (uint32_t)(__ffsll((long long)f0) - 1) >> 3;
-        f0 &= f0 - 1;
-      } else {
-        k = 8 + ((uint32_t)(__ffsll((long long)f1) - 1) >> 3);
-        f1 &= f1 - 1;
-      }
-      const uint64_t p = p0 + k;
-      uint64_t size;
-      if (p < n && sfwp::block_message(data + p, n - p, &size)) mask |= 1u << k;
-    }
+// Only a position that holds 'F' is looked at further: most lanes have one (a
+// message is about 37 bytes).
+struct BlockRules {
+  static constexpr uint32_t kFirst = 'F', kSecond = 0;
+  static __device__ __forceinline__ uint32_t message(const uint8_t* b, uint64_t avail, uint32_t*, uint64_t* size) {
+    return sfwp::block_message(b, avail, size);
   }
-  // lanes 4j .. 4j + 3 hold positions [64 (g / 4), + 64)
-  unsigned long long m = mask;
-  m |= (unsigned long long)__shfl_down(mask, 1) << 16;
-  m |= (unsigned long long)__shfl_down(mask, 2) << 32;
-  m |= (unsigned long long)__shfl_down(mask, 3) << 48;
-  if ((threadIdx.x & 3) == 0 && p0 < n) {
-    words[g >> 2] = m;
-    counts[g >> 2] = (uint32_t)__popcll(m);
-  }
-}
+};
 
 // The length (34..48) and size of the message at candidate position p: the
 // tag and the digest's newline were checked when p became a candidate.
@@ -178,12 +125,7 @@ __global__ void __launch_bounds__(256) recv_extract_kernel(const uint8_t* __rest
     if (i == k - 1) res->end = p + L;
     if (size > 0xFFFFFFFFull) atomicOr(&res->too_large, 1u);
     if (i >= cap) continue;
-    const uint8_t* d = data + p + sfwp::kTag;  // no alignment: bytes, stored as the table's dwords
-    uint32_t* o = digests + 5 * i;
-#pragma unroll
-    for (int j = 0; j < 5; j++)
-      o[j] = (uint32_t)d[4 * j] | (uint32_t)d[4 * j + 1] << 8 | (uint32_t)d[4 * j + 2] << 16 |
-             (uint32_t)d[4 * j + 3] << 24;
+    store_digest(digests + 5 * i, data + p + sfwp::kTag);
     sizes[i] = (uint32_t)size;
   }
 }
@@ -198,21 +140,11 @@ inline void reset_stats() {
   for (auto& v : g_parse_stats) v.store(0, std::memory_order_relaxed);
 }
 
-inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 }  // namespace
 
 using namespace sfi;
 
 namespace {
-
-// Stream-ordered scratch that goes back on every path out of a call.
-struct Scratch {
-  void* p = nullptr;
-  hipStream_t s;
-  explicit Scratch(hipStream_t s_) : s(s_) {}
-  ~Scratch() { stream_free(p, s); }
-};
 
 struct Parsed {
   uint64_t count = 0, consumed = 0;
@@ -261,42 +193,16 @@ int parse_on_host(const uint8_t* d_wire, const uint8_t* h_wire, uint64_t n, uint
 int parse_run_device(const uint8_t* d_wire, const uint8_t* h_wire, uint64_t n, uint8_t* d_digests, uint32_t* d_sizes,
                      uint64_t cap, Parsed* out, hipStream_t s, HostLease* lease) {
   if (knob(K_TEST_WIRE_PARSE_HOST) == 1) return parse_on_host(d_wire, h_wire, n, d_digests, d_sizes, cap, out, s, lease);
-  const uint64_t nw = ceil_div(n, 64);
-  size_t tmp = 0;
-  {
-    uint32_t* in = nullptr;
-    uint64_t* o = nullptr;
-    if (rocprim::inclusive_scan(nullptr, tmp, in, o, (size_t)nw, rocprim::plus<uint64_t>(), s) != hipSuccess) {
-      (void)hipGetLastError();
-      return SF_ENODEV;
-    }
-  }
-  const size_t wb = align256(nw * 8), cb = align256(nw * 4);
-  Scratch ws(s);
-  int rc = stream_alloc(&ws.p, 256 + 2 * wb + cb + tmp + 8, s);
+  Scan sc(s);
+  const int rc = scan_candidates<BlockRules>(d_wire, n, s, &sc);
   if (rc != SF_OK) return rc;
-  uint8_t* base = static_cast<uint8_t*>(ws.p);
-  Result* res = reinterpret_cast<Result*>(base);
-  unsigned long long* words = reinterpret_cast<unsigned long long*>(base + 256);
-  uint64_t* ends = reinterpret_cast<uint64_t*>(base + 256 + wb);
-  uint32_t* counts = reinterpret_cast<uint32_t*>(base + 256 + 2 * wb);
-  void* scan_tmp = base + 256 + 2 * wb + cb;
-  SF_HIP(hipMemsetAsync(res, 0, sizeof(Result), s));
-  SF_HIP(hipMemsetAsync(&res->first_bad, 0xFF, sizeof(res->first_bad), s));
+  Result* res = static_cast<Result*>(sc.result);
+  const dim3 gw((unsigned)ceil_div(sc.nw, 256));
   clear_stale_error();
-  hipLaunchKernelGGL(recv_candidates_kernel, dim3((unsigned)ceil_div(n, 256 * kPerLane)), dim3(256), 0, s, d_wire, n,
-                     words, counts);
-  SF_HIP(hipGetLastError());
-  if (rocprim::inclusive_scan(scan_tmp, tmp, counts, ends, (size_t)nw, rocprim::plus<uint64_t>(), s) != hipSuccess) {
-    (void)hipGetLastError();
-    return SF_ENODEV;
-  }
-  const dim3 gw((unsigned)ceil_div(nw, 256));
-  clear_stale_error();
-  hipLaunchKernelGGL(recv_chain_kernel, gw, dim3(256), 0, s, d_wire, n, words, ends, nw, res);
+  hipLaunchKernelGGL(recv_chain_kernel, gw, dim3(256), 0, s, d_wire, n, sc.words, sc.ends, sc.nw, res);
   SF_HIP(hipGetLastError());
   clear_stale_error();
-  hipLaunchKernelGGL(recv_extract_kernel, gw, dim3(256), 0, s, d_wire, n, words, ends, nw,
+  hipLaunchKernelGGL(recv_extract_kernel, gw, dim3(256), 0, s, d_wire, n, sc.words, sc.ends, sc.nw,
                      reinterpret_cast<uint32_t*>(d_digests), d_sizes, cap, res);
   SF_HIP(hipGetLastError());
   Result h{};
@@ -411,8 +317,6 @@ int receive_device(const ReceiveArgs& a, const uint8_t* d_wire, const uint8_t* h
   return SF_OK;
 }
 
-constexpr uint64_t kUploadPiece = 64ull << 20;  // bytes of the run per pinned stage
-
 int receive_buffer(const sf_block_set* set, const uint8_t* wire, uint64_t n_bytes, uint64_t base_offset,
                    sf_block_sig* out, int64_t* src_rows, uint64_t cap, uint64_t* n_out, uint64_t* consumed,
                    int* stop, uint64_t* end_offset) {
@@ -425,27 +329,8 @@ int receive_buffer(const sf_block_set* set, const uint8_t* wire, uint64_t n_byte
   hipEvent_t* ev;
   if ((rc = res.streams(st, ev)) != SF_OK) return rc;
   hipStream_t s = st[0];
-  // the run to HBM through the two pinned stages
-  void* d_wire = nullptr;
-  if ((rc = res.dev(kSlotFileTable, n_bytes, &d_wire)) != SF_OK) return rc;
-  const uint64_t piece = std::min(n_bytes, kUploadPiece);
-  void* pin[2] = {nullptr, nullptr};
-  for (int b = 0; b < 2; b++)
-    if ((rc = res.pin(kSlotData + b, piece, &pin[b])) != SF_OK) return rc;
-  rc = two_stage(
-      ceil_div(n_bytes, piece),
-      [&](uint64_t k, int b) {
-        const uint64_t o = k * piece, m = std::min(piece, n_bytes - o);
-        memcpy(pin[b], wire + o, m);
-        SF_HIP(hipMemcpyAsync(static_cast<uint8_t*>(d_wire) + o, pin[b], m, hipMemcpyHostToDevice, s));
-        SF_HIP(hipEventRecord(ev[b], s));
-        return SF_OK;
-      },
-      [&](uint64_t, int b) {
-        SF_HIP(hipEventSynchronize(ev[b]));
-        return SF_OK;
-      });
-  if (rc != SF_OK) return rc;
+  const uint8_t* d_wire = nullptr;
+  if ((rc = upload_run(res, wire, n_bytes, s, ev, &d_wire)) != SF_OK) return rc;
   // device rows for every message the run can hold: offsets, rows, sizes
   const uint64_t most = n_bytes / sfwp::kMinMessage + 1;
   void *ddig = nullptr, *daux = nullptr;
@@ -456,7 +341,7 @@ int receive_buffer(const sf_block_set* set, const uint8_t* wire, uint64_t n_byte
   a.d_rows = reinterpret_cast<int64_t*>(a.d_offsets + most);
   a.d_sizes = reinterpret_cast<uint32_t*>(a.d_rows + most);
   a.cap = most;
-  if ((rc = receive_device(a, static_cast<const uint8_t*>(d_wire), wire, n_bytes, s, &res)) != SF_OK) return rc;
+  if ((rc = receive_device(a, d_wire, wire, n_bytes, s, &res)) != SF_OK) return rc;
   const uint64_t n = *n_out;
   if (n > cap) return SF_ENOSPC;
   if (n == 0) return SF_OK;

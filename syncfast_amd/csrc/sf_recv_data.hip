@@ -1,8 +1,8 @@
 // sf_recv_data.hip -- a received run of BLOCK_DATA messages on the device
 // (include/syncfast_amd.h: sf_receive_block_data_device / _buffer): parsed as
 // the reference parser reads it, every payload hashed in place and compared
-// with the digest its message claims.  The data-side twin of sf_recv.hip, in
-// its own translation unit: the other kernels' code objects stay as they are.
+// with the digest its message claims.  Beside sf_recv.hip, in its own
+// translation unit: the other kernels' code objects stay as they are.
 //
 // A message is a header of H = 34 to 48 bytes (sf_wire_data.hpp has the
 // rules), `size` payload bytes and a newline.  Unlike a FILE_BLOCK message
@@ -11,12 +11,9 @@
 // may announce a length that lands on a later message's end byte.  The steps,
 // ordered by kernel boundaries only (no lane waits for another):
 //
-//   candidates  every byte position p is tested (a lane takes 16 of them): p
-//               is a candidate when a whole, valid message stands there
-//               (data_message, the function the host parser uses).  Every
-//               true message start is one; payload bytes may make others.
-//               64 positions' flags are one word of a bitmap and one count.
-//   scan        rocprim inclusive scan of the counts; the candidate total is
+//   candidates, scan   sf_recv_scan.hpp, shared with sf_recv.hip: the bitmap
+//               of every position where data_message holds, and every
+//               candidate's index in position order.  The candidate total is
 //               read back (the call blocks there).
 //   compact     one lane per bitmap word writes pos[i] and len[i] (8 B each)
 //               of its candidates, in position order.
@@ -41,22 +38,19 @@
 //               where they lie, d_data = d_wire; a compare kernel writes one
 //               byte per message and counts the mismatches.
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 #include <string.h>
 
 #include <memory>
 
-#include <rocprim/device/device_scan.hpp>
-
-#include "sf_internal.hpp"
-#include "sf_stage.hpp"
+#include "sf_recv_scan.hpp"
 #include "sf_wire_data.hpp"
 #include "../../include/syncfast_amd_test.h"
 
-namespace {
+using namespace sfrs;
 
-constexpr uint64_t kMaxRun = 1ull << 38;  // bytes per call: every grid stays far below 2^31 workgroups
-constexpr uint32_t kPerLane = 16;         // byte positions per lane of the candidates kernel
+namespace {
 
 // What the host reads back, in one copy.
 struct Result {
@@ -66,66 +60,18 @@ struct Result {
   uint8_t tail[sfwp::kMaxMessage];  // the run's bytes from E on (to its end, if that comes first)
 };
 
-// 0x80 in exactly the bytes of v that equal c
-__device__ __forceinline__ uint32_t bytes_equal(uint32_t v, uint32_t c) {
-  const uint32_t x = v ^ (c * 0x01010101u);
-  return ~(((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x | 0x7F7F7F7Fu);
-}
+static_assert(offsetof(Result, first_bad) == 0 && sizeof(Result::first_bad) == 8 && sizeof(Result) <= 256,
+              "sfrs::Scan::result: 256 bytes that begin with first_bad");
 
-// One lane per 16 byte positions [p0, p0 + 16): their bytes come as aligned
-// dwords shifted into place where all five lie inside [data, data + n), else
-// byte by byte, so nothing outside the run is read.  Only a position that
-// holds 'B' with 'L' after it (the sixteenth: 'B' alone, its neighbour is
-// another lane's) is looked at further -- a payload of 'B's costs no more
-// than any other.  Four lanes' flags make one word of the bitmap.
-__global__ void __launch_bounds__(256) data_candidates_kernel(const uint8_t* __restrict__ data, uint64_t n,
-                                                              unsigned long long* __restrict__ words,
-                                                              uint32_t* __restrict__ counts) {
-  const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const uint64_t p0 = g * kPerLane;
-  uint32_t w[4] = {0, 0, 0, 0}, mask = 0;
-  if (p0 < n) {
-    const uint32_t a = (uint32_t)(reinterpret_cast<uintptr_t>(data) & 3u);  // the same for every lane: p0 is a multiple of 16
-    if (p0 >= a && p0 - a + kPerLane + 4 <= n) {
-      const uint32_t* q = reinterpret_cast<const uint32_t*>(data + p0 - a);
-      const uint32_t d[5] = {q[0], q[1], q[2], q[3], a ? q[4] : 0u};
-#pragma unroll
-      for (int j = 0; j < 4; j++) w[j] = __funnelshift_r(d[j], d[j + 1], 8 * a);
-    } else {
-      const uint32_t m = n - p0 < kPerLane ? (uint32_t)(n - p0) : kPerLane;
-      for (uint32_t k = 0; k < m; k++) w[k >> 2] |= (uint32_t)data[p0 + k] << (8 * (k & 3));
-    }
-    const unsigned long long b0 = bytes_equal(w[0], 'B') | (unsigned long long)bytes_equal(w[1], 'B') << 32;
-    const unsigned long long b1 = bytes_equal(w[2], 'B') | (unsigned long long)bytes_equal(w[3], 'B') << 32;
-    const unsigned long long l0 = bytes_equal(w[0], 'L') | (unsigned long long)bytes_equal(w[1], 'L') << 32;
-    const unsigned long long l1 = bytes_equal(w[2], 'L') | (unsigned long long)bytes_equal(w[3], 'L') << 32;
-    unsigned long long f0 = b0 & ((l0 >> 8) | (l1 << 56));
-    unsigned long long f1 = b1 & ((l1 >> 8) | 0x8000000000000000ull);
-    while (f0 | f1) {
-      uint32_t k;
-      if (f0) {
-        k = (uint32_t)(__ffsll((long long)f0) - 1) >> 3;
-        f0 &= f0 - 1;
-      } else {
-        k = 8 + ((uint32_t)(__ffsll((long long)f1) - 1) >> 3);
-        f1 &= f1 - 1;
-      }
-      const uint64_t p = p0 + k;
-      uint32_t H;
-      uint64_t size;
-      if (p < n && sfwp::data_message(data + p, n - p, &H, &size)) mask |= 1u << k;
-    }
+// Only a position that holds 'B' with 'L' after it (the sixteenth: 'B' alone,
+// its neighbour is another lane's) is looked at further -- a payload of 'B's
+// costs no more than any other.
+struct DataRules {
+  static constexpr uint32_t kFirst = 'B', kSecond = 'L';
+  static __device__ __forceinline__ uint64_t message(const uint8_t* b, uint64_t avail, uint32_t* H, uint64_t* size) {
+    return sfwp::data_message(b, avail, H, size);
   }
-  // lanes 4j .. 4j + 3 hold positions [64 (g / 4), + 64)
-  unsigned long long m = mask;
-  m |= (unsigned long long)__shfl_down(mask, 1) << 16;
-  m |= (unsigned long long)__shfl_down(mask, 2) << 32;
-  m |= (unsigned long long)__shfl_down(mask, 3) << 48;
-  if ((threadIdx.x & 3) == 0 && p0 < n) {
-    words[g >> 2] = m;
-    counts[g >> 2] = (uint32_t)__popcll(m);
-  }
-}
+};
 
 // One lane per bitmap word: position and length of its candidates, at their
 // index in position order (ends: the inclusive scan of the counts).
@@ -184,12 +130,7 @@ __global__ void __launch_bounds__(256) data_extract_kernel(const uint8_t* __rest
   }
   if (size > 0xFFFFFFFFull) atomicOr(&res->too_large, 1u);
   if (k >= cap) return;
-  const uint8_t* d = data + p + sfwp::kTag;  // no alignment: bytes, stored as the table's dwords
-  uint32_t* o = digests + 5 * k;
-#pragma unroll
-  for (int j = 0; j < 5; j++)
-    o[j] = (uint32_t)d[4 * j] | (uint32_t)d[4 * j + 1] << 8 | (uint32_t)d[4 * j + 2] << 16 |
-           (uint32_t)d[4 * j + 3] << 24;
+  store_digest(digests + 5 * k, data + p + sfwp::kTag);
   sizes[k] = (uint32_t)size;
   offsets[k] = p + H;
 }
@@ -220,21 +161,11 @@ inline void reset_stats() {
   for (auto& v : g_data_stats) v.store(0, std::memory_order_relaxed);
 }
 
-inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 }  // namespace
 
 using namespace sfi;
 
 namespace {
-
-// Stream-ordered scratch that goes back on every path out of a call.
-struct Scratch {
-  void* p = nullptr;
-  hipStream_t s;
-  explicit Scratch(hipStream_t s_) : s(s_) {}
-  ~Scratch() { stream_free(p, s); }
-};
 
 struct Outputs {
   void* d_digests = nullptr;
@@ -343,38 +274,12 @@ int parse_run_device(const uint8_t* d_wire, const uint8_t* h_wire, uint64_t n, c
 int find_messages(const uint8_t* d_wire, const uint8_t* h_wire, uint64_t n, const Provide& provide, Outputs* o,
                   Parsed* out, hipStream_t s, HostLease* lease) {
   const int64_t force = knob(K_TEST_BLOCK_DATA_WALK);
-  const uint64_t nw = ceil_div(n, 64);
-  size_t tmp = 0;
-  {
-    uint32_t* in = nullptr;
-    uint64_t* e = nullptr;
-    if (rocprim::inclusive_scan(nullptr, tmp, in, e, (size_t)nw, rocprim::plus<uint64_t>(), s) != hipSuccess) {
-      (void)hipGetLastError();
-      return SF_ENODEV;
-    }
-  }
-  const size_t wb = align256(nw * 8), cb = align256(nw * 4);
-  Scratch ws(s);
-  int rc = stream_alloc(&ws.p, 256 + 2 * wb + cb + tmp + 8, s);
+  Scan sc(s);
+  int rc = scan_candidates<DataRules>(d_wire, n, s, &sc);
   if (rc != SF_OK) return rc;
-  uint8_t* base = static_cast<uint8_t*>(ws.p);
-  Result* res = reinterpret_cast<Result*>(base);
-  unsigned long long* words = reinterpret_cast<unsigned long long*>(base + 256);
-  uint64_t* ends = reinterpret_cast<uint64_t*>(base + 256 + wb);
-  uint32_t* counts = reinterpret_cast<uint32_t*>(base + 256 + 2 * wb);
-  void* scan_tmp = base + 256 + 2 * wb + cb;
-  SF_HIP(hipMemsetAsync(res, 0, sizeof(Result), s));
-  SF_HIP(hipMemsetAsync(&res->first_bad, 0xFF, sizeof(res->first_bad), s));
-  clear_stale_error();
-  hipLaunchKernelGGL(data_candidates_kernel, dim3((unsigned)ceil_div(n, 256 * kPerLane)), dim3(256), 0, s, d_wire, n,
-                     words, counts);
-  SF_HIP(hipGetLastError());
-  if (rocprim::inclusive_scan(scan_tmp, tmp, counts, ends, (size_t)nw, rocprim::plus<uint64_t>(), s) != hipSuccess) {
-    (void)hipGetLastError();
-    return SF_ENODEV;
-  }
+  Result* res = static_cast<Result*>(sc.result);
   uint64_t total = 0;
-  SF_HIP(hipMemcpyAsync(&total, ends + nw - 1, 8, hipMemcpyDeviceToHost, s));
+  SF_HIP(hipMemcpyAsync(&total, sc.ends + sc.nw - 1, 8, hipMemcpyDeviceToHost, s));
   SF_HIP(hipStreamSynchronize(s));
   g_data_stats[0].store(total, std::memory_order_relaxed);
   if (total > n / sfwp::kTag + 1) return SF_EIO;  // cannot be: two candidates' tags do not overlap
@@ -387,7 +292,8 @@ int find_messages(const uint8_t* d_wire, const uint8_t* h_wire, uint64_t n, cons
     uint64_t* pos = static_cast<uint64_t*>(list.p);
     uint64_t* len = pos + total;
     clear_stale_error();
-    hipLaunchKernelGGL(data_compact_kernel, grid_for(nw), dim3(256), 0, s, d_wire, n, words, ends, nw, total, pos, len);
+    hipLaunchKernelGGL(data_compact_kernel, grid_for(sc.nw), dim3(256), 0, s, d_wire, n, sc.words, sc.ends, sc.nw, total,
+                       pos, len);
     SF_HIP(hipGetLastError());
     clear_stale_error();
     hipLaunchKernelGGL(data_link_kernel, grid_for(total), dim3(256), 0, s, pos, len, total, res);
@@ -487,8 +393,6 @@ int report(const Results& r, const Parsed& p, uint64_t cap) {
   return p.count > cap ? SF_ENOSPC : SF_OK;
 }
 
-constexpr uint64_t kUploadPiece = 64ull << 20;  // bytes of the run per pinned stage
-
 int receive_buffer(const uint8_t* wire, uint64_t n_bytes, sf_block_sig* out, uint8_t* ok, uint64_t cap,
                    const Results& r) {
   int rc = check_args(r, wire, n_bytes);
@@ -499,27 +403,8 @@ int receive_buffer(const uint8_t* wire, uint64_t n_bytes, sf_block_sig* out, uin
   hipEvent_t* ev;
   if ((rc = res.streams(st, ev)) != SF_OK) return rc;
   hipStream_t s = st[0];
-  // the run to HBM through the two pinned stages
-  void* d_wire = nullptr;
-  if ((rc = res.dev(kSlotFileTable, n_bytes, &d_wire)) != SF_OK) return rc;
-  const uint64_t piece = std::min(n_bytes, kUploadPiece);
-  void* pin[2] = {nullptr, nullptr};
-  for (int b = 0; b < 2; b++)
-    if ((rc = res.pin(kSlotData + b, piece, &pin[b])) != SF_OK) return rc;
-  rc = two_stage(
-      ceil_div(n_bytes, piece),
-      [&](uint64_t k, int b) {
-        const uint64_t o = k * piece, m = std::min(piece, n_bytes - o);
-        memcpy(pin[b], wire + o, m);
-        SF_HIP(hipMemcpyAsync(static_cast<uint8_t*>(d_wire) + o, pin[b], m, hipMemcpyHostToDevice, s));
-        SF_HIP(hipEventRecord(ev[b], s));
-        return SF_OK;
-      },
-      [&](uint64_t, int b) {
-        SF_HIP(hipEventSynchronize(ev[b]));
-        return SF_OK;
-      });
-  if (rc != SF_OK) return rc;
+  const uint8_t* d_wire = nullptr;
+  if ((rc = upload_run(res, wire, n_bytes, s, ev, &d_wire)) != SF_OK) return rc;
   // device rows for the messages once they are counted (none when the
   // caller has no room for them: SF_ENOSPC): offsets, sizes, ok bytes
   void *ddig = nullptr, *daux = nullptr;
@@ -537,7 +422,7 @@ int receive_buffer(const uint8_t* wire, uint64_t n_bytes, sf_block_sig* out, uin
   };
   Outputs o;
   Parsed p;
-  rc = parse_run_device(static_cast<const uint8_t*>(d_wire), wire, n_bytes, provide, &o, &p, s, &res);
+  rc = parse_run_device(d_wire, wire, n_bytes, provide, &o, &p, s, &res);
   if (rc != SF_OK) return rc;
   if ((rc = report(r, p, cap)) != SF_OK) return rc;
   const uint64_t n = p.count;

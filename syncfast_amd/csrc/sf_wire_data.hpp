@@ -21,7 +21,7 @@ namespace sfwp {
 
 // Not a stop: a whole BLOCK_DATA message (classify_data) or a whole header
 // (data_header) stands there.
-constexpr int kData = -1;
+constexpr int kData = kHeader;
 
 constexpr uint32_t kMinData = kMinMessage + 1;  // 35: an empty payload and its end byte
 
@@ -51,23 +51,7 @@ constexpr uint64_t data_message(const uint8_t* b, uint64_t avail, uint32_t* H, u
 // when a whole valid header stands there, else why a BLOCK_DATA run stops
 // here -- FILE_BLOCK is one of the other commands now.
 inline int data_header(const uint8_t* b, uint64_t avail, uint32_t* H, uint64_t* size) {
-  *H = 0;
-  if (avail == 0) return kEnd;
-  bool raise = false;
-  const int c = line_end(b, avail, kCommandMax, &raise);
-  if (c < 0) return raise ? kMalformed : kIncomplete;  // "Unterminated command"
-  static const char* const others[8] = {"FILE_ENTRY", "END_FILES",  "GET_FILE",   "FILE_START",
-                                        "FILE_END",   "GET_BLOCK",  "FILE_BLOCK", "COMPLETE"};
-  for (const char* o : others)
-    if (strlen(o) == (size_t)c && memcmp(b, o, (size_t)c) == 0) return kOther;
-  if (c != (int)kTag - 1 || memcmp(b, "BLOCK_DATA", kTag - 1) != 0) return kMalformed;  // "Unknown command"
-  if (avail < kTag + kDigest + 1) return kIncomplete;
-  if (b[kTag + kDigest] != '\n') return kMalformed;  // "Unterminated digest"
-  const int s = line_end(b + kSizeAt, avail - kSizeAt, kSizeMax, &raise);
-  if (s < 0) return raise ? kMalformed : kIncomplete;  // "Unterminated length"
-  if (!size_value(b + kSizeAt, (uint32_t)s, size)) return kMalformed;  // "Invalid block length"
-  *H = kSizeAt + (uint32_t)s + 1;
-  return kData;
+  return header(b, avail, "BLOCK_DATA", H, size);
 }
 
 // What stands at b (avail bytes to the end of the buffer): kData with the

@@ -1,7 +1,8 @@
 // sf_wire_parse.hpp -- the framing rules of the reference's message parser
 // (src/sync/ssh/proto.rs:189-477, mirrored by syncfast_amd/wire.py's Parser)
 // for a run of FILE_BLOCK messages, restated in C++: one message at a known
-// start (block_message), what stops a run (classify) and the serial parse of
+// start (block_message), what stops a run (classify, through header, which
+// reads a BLOCK_DATA header for sf_wire_data.hpp too) and the serial parse of
 // a whole run on the host (parse_run) -- the fallback of
 // sf_wire_parse_blocks_device and the parser of sf_receive_blocks_buffer's.
 //
@@ -17,8 +18,9 @@ namespace sfwp {
 
 // SF_WIRE_* of include/syncfast_amd.h
 constexpr int kEnd = 0, kIncomplete = 1, kOther = 2, kMalformed = 3;
-// Not a stop: a whole FILE_BLOCK message stands there (classify only).
-constexpr int kBlock = -1;
+// Not a stop: a whole header of the run's own tag stands there (header);
+// for a FILE_BLOCK run that is a whole message (classify only).
+constexpr int kHeader = -1, kBlock = kHeader;
 
 // Limits of the reference parser (proto.rs:249-251) and what follows from
 // them: "FILE_BLOCK\n" + 20 digest bytes + "\n" + a size field of 1 to 15
@@ -78,26 +80,38 @@ inline int line_end(const uint8_t* b, uint64_t avail, uint32_t limit, bool* rais
   return -1;
 }
 
-// What stands at b (avail bytes to the end of the buffer): kBlock with its
-// length and size, or why a FILE_BLOCK run stops here.
-inline int classify(const uint8_t* b, uint64_t avail, uint32_t* len, uint64_t* size) {
+// The header at b, read from its first min(avail, 48) bytes alone (avail: the
+// bytes to the end of the buffer), for a run of `tag` messages ("FILE_BLOCK"
+// or "BLOCK_DATA": ten bytes, digest and size field laid out alike): kHeader
+// with its length and the value of its size field when a whole valid header
+// of that tag stands there, else why the run stops here.  The other of the
+// two tags is one of the other commands then.
+inline int header(const uint8_t* b, uint64_t avail, const char* tag, uint32_t* len, uint64_t* size) {
   *len = 0;
   if (avail == 0) return kEnd;
   bool raise = false;
   const int c = line_end(b, avail, kCommandMax, &raise);
-  if (c < 0) return raise ? kMalformed : kIncomplete;
-  static const char* const others[8] = {"FILE_ENTRY", "END_FILES",  "GET_FILE",   "FILE_START",
-                                        "FILE_END",   "GET_BLOCK",  "BLOCK_DATA", "COMPLETE"};
-  for (const char* o : others)
-    if (strlen(o) == (size_t)c && memcmp(b, o, (size_t)c) == 0) return kOther;
-  if (c != (int)kTag - 1 || memcmp(b, "FILE_BLOCK", kTag - 1) != 0) return kMalformed;  // "Unknown command"
+  if (c < 0) return raise ? kMalformed : kIncomplete;  // "Unterminated command"
+  if (c != (int)kTag - 1 || memcmp(b, tag, kTag - 1) != 0) {
+    static const char* const commands[9] = {"FILE_ENTRY", "END_FILES",  "GET_FILE",   "FILE_START", "FILE_END",
+                                            "GET_BLOCK",  "FILE_BLOCK", "BLOCK_DATA", "COMPLETE"};
+    for (const char* o : commands)
+      if (strlen(o) == (size_t)c && memcmp(b, o, (size_t)c) == 0) return kOther;
+    return kMalformed;  // "Unknown command"
+  }
   if (avail < kTag + kDigest + 1) return kIncomplete;
   if (b[kTag + kDigest] != '\n') return kMalformed;  // "Unterminated digest"
   const int s = line_end(b + kSizeAt, avail - kSizeAt, kSizeMax, &raise);
-  if (s < 0) return raise ? kMalformed : kIncomplete;  // "Unterminated size"
-  if (!size_value(b + kSizeAt, (uint32_t)s, size)) return kMalformed;  // "Invalid block size"
+  if (s < 0) return raise ? kMalformed : kIncomplete;  // "Unterminated size" / "Unterminated length"
+  if (!size_value(b + kSizeAt, (uint32_t)s, size)) return kMalformed;  // "Invalid block size" / "Invalid block length"
   *len = kSizeAt + (uint32_t)s + 1;
-  return kBlock;
+  return kHeader;
+}
+
+// What stands at b (avail bytes to the end of the buffer): kBlock with its
+// length and size, or why a FILE_BLOCK run stops here.
+inline int classify(const uint8_t* b, uint64_t avail, uint32_t* len, uint64_t* size) {
+  return header(b, avail, "FILE_BLOCK", len, size);
 }
 
 // The run at b[0, n), message after message as the reference parser reads it:

@@ -11,7 +11,9 @@ import numpy as np
 import pytest
 import torch
 
+import data_expect
 import oracle
+import recv_forge
 import syncfast_amd
 from recv_expect import END, INCOMPLETE, MALFORMED, OTHER, expected, message
 from syncfast_amd import _lib, host, wire
@@ -149,6 +151,29 @@ def test_hostile_digests(gpu, fill):
     assert len(expected(run)[0]) == len(digests) and expected(run)[3] == END
     _check(run, gpu)
     _check(run + b"FILE_END\n", gpu)
+
+
+@pytest.mark.parametrize("lead", [0, 3])
+def test_block_data_messages_in_the_digests_and_after_the_run(gpu, lead):
+    """The other receive parser's message kind as the hostile content: every
+    digest holds the BLOCK_DATA tag and goes on like a data header, the second
+    and third so that a whole BLOCK_DATA message stands inside the run, and
+    one follows it.  None of that is a FILE_BLOCK candidate."""
+    fill = b"\xaa"
+    # the data header in the second digest reaches over the third message's tag, whose newline ends its
+    # digest; its length field, its payload and its end byte are the third digest's first bytes
+    digests = [b"BLOCK_DATA\n" + bytes(8) + b"\n",
+               fill * 4 + b"BLOCK_DATA\n" + fill * 5,
+               b"4\nabcd\n" + b"BLOCK_DATA\n" + fill * 2]
+    three = b"".join(message(d, s) for d, s in zip(digests, (5, 123, 4294967295)))
+    run = three + data_expect.message(b"BLOCK_DATA\n" + b"FILE_BLOC" + fill * 30)
+    inside = [p for p, _ in data_expect.candidates(run) if p < len(three)]
+    assert inside == [len(message(digests[0], 5)) + 11 + 4]  # a whole message to the parser, started there
+    assert 100 < len(run) < 400
+    want_d, _, want_c, want_stop = expected(run)
+    assert (want_d, want_c, want_stop) == (digests, len(three), OTHER)
+    stats = _check(run, gpu, lead)
+    assert stats[0] == len(recv_forge.candidates(run)) == 3 and stats[2] == 0
 
 
 def _forged():

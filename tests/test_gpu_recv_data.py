@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+import recv_expect
 import syncfast_amd
 from data_expect import (END, INCOMPLETE, MALFORMED, OTHER, OTHERS, TAG, candidates, dense_run, expected, header,
                          honest_run, message, needs_walk)
@@ -109,6 +110,25 @@ def test_placement_in_the_allocation(gpu, lead):
     run = honest_run(random.Random(11), 14)
     _, stats = _check(run, gpu, lead)
     assert stats[2] == 0
+
+
+@pytest.mark.parametrize("lead", [0, 3])
+def test_file_block_messages_as_payloads_and_after_the_run(gpu, lead):
+    """The other receive parser's message kind as the hostile content: every
+    payload is a whole FILE_BLOCK message (the shortest, the longest and one
+    between), and one follows the run.  None of that is a BLOCK_DATA
+    candidate."""
+    rng = random.Random(13)
+    payloads = [recv_expect.message(rng.randbytes(20), size) for size in (b"7", b"4294967295", b"+00000000000012")]
+    assert [len(p) for p in payloads] == [34, 43, 48]
+    three = b"".join(message(p) for p in payloads)
+    run = three + recv_expect.message(rng.randbytes(20), 99)
+    assert len(recv_expect.expected(run[len(three):])[0]) == 1 and 100 < len(run) < 400
+    want = expected(run)
+    assert (want[1], want[3], want[4]) == ([34, 43, 48], len(three), OTHER)
+    got, stats = _check(run, gpu, lead)
+    assert got[3].cpu().numpy().tolist() == [1, 1, 1]
+    assert stats[0] == len(candidates(run)) == 3 and stats[2] == 0
 
 
 @pytest.mark.parametrize("at", [15, 16, 63, 64])
