@@ -69,7 +69,9 @@ class FileImages:
     ``temp_name("a.bin")`` -- to the size FILE_END fixed for it.  An image has
     exactly that size: it starts zero-filled at a 256-byte-aligned base of the
     allocation, so one ``copy_blocks`` call serves all files at once, and it
-    never grows.
+    never grows.  The zero fill runs on the stream that is current at
+    construction; ``apply_copies``, ``apply_writes`` and ``write`` on another
+    ``stream`` wait for it there.
     """
 
     ALIGN = 256
@@ -89,6 +91,10 @@ class FileImages:
             self._size[_name_str(name)] = size
             at += (size + self.ALIGN - 1) // self.ALIGN * self.ALIGN
         self.buffer = torch.zeros(max(at, 1), dtype=torch.uint8, device=self.device)
+        # the zero fill runs on the stream current here; a copy or a write on
+        # another stream waits for it (_after_fill)
+        self._filled = torch.cuda.Event()
+        self._filled.record(torch.cuda.current_stream(self.device))
         self._local: Dict[str, torch.Tensor] = {}
         self._copied: Dict[str, set] = {}  # per image: the offsets apply_copies filled (present at FILE_END)
 
@@ -106,14 +112,23 @@ class FileImages:
             raise ValueError(f"bytes [{offset}, {offset + size}) end past the {self._size[key]} bytes of {key}")
         return self._base[key] + offset
 
+    def _after_fill(self, stream) -> None:
+        """`stream` (None: the current one) ordered after the zero fill, and
+        the allocation marked as in use on it."""
+        s = stream if stream is not None else torch.cuda.current_stream(self.device)
+        s.wait_event(self._filled)
+        self.buffer.record_stream(s)
+
     def _copy(self, src: torch.Tensor, jobs: List[tuple], stream) -> None:
         """jobs = [(src_offset, dst_offset in the allocation, size)]."""
         if not jobs:
             return
         a = np.asarray(jobs, dtype=np.int64).reshape(-1, 3)
-        so = torch.from_numpy(a[:, 0].copy()).to(self.device)
-        do = torch.from_numpy(a[:, 1].copy()).to(self.device)
-        sz = torch.from_numpy(a[:, 2].astype(np.uint32).view(np.int32)).to(self.device)
+        self._after_fill(stream)
+        with _device._on(self.device, stream):  # the lists belong to the stream the copy runs on
+            so = torch.from_numpy(a[:, 0].copy()).to(self.device)
+            do = torch.from_numpy(a[:, 1].copy()).to(self.device)
+            sz = torch.from_numpy(a[:, 2].astype(np.uint32).view(np.int32)).to(self.device)
         _device.copy_blocks(src, self.buffer, so, do, sz, stream=stream)
 
     def apply_writes(self, writes, data, stream: Optional[torch.cuda.Stream] = None) -> int:
@@ -233,4 +248,5 @@ class FileImages:
     def write(self, name, fd: int, stream: Optional[torch.cuda.Stream] = None) -> int:
         """The image of ``name`` written from byte 0 of the open file ``fd``
         (``device.write_to_fd``); returns the bytes written."""
+        self._after_fill(stream)
         return _device.write_to_fd(self.image(name), fd, 0, stream=stream)
