@@ -22,6 +22,19 @@
  *  - Digests are the 20 bytes of sha1.digest().bytes() (big-endian SHA-1),
  *    exactly HashDigest's field (src/lib.rs:72-76), stored back to back:
  *    block i at byte 20*i.
+ *  - Output alignment.  A device output must be aligned to the widest store
+ *    a kernel makes to it; each entry point names it, and a pointer that is
+ *    not (NULL is) gives SF_EINVAL before anything is launched:
+ *      4 B  digest tables and blocks_hash tables (d_digests, d_file_hashes:
+ *           five 32-bit stores per row, and a 20-B row pitch keeps every row
+ *           4-B aligned), uint32 / int32 arrays and a written d_status;
+ *      8 B  uint64 / int64 arrays (d_offsets, d_data_offsets, d_rows);
+ *      1 B  wire bytes (d_out), d_ok, and the destination of a block copy.
+ *    Inputs need no alignment beyond their element type's unless stated.
+ *  - Written extent.  A call writes the rows of its outputs it reports (or
+ *    the first cap of them, where stated) and no other byte of the caller's
+ *    memory: not the rows past them, not a byte before or after an output,
+ *    and never an input.
  *  - Fixed tiling: block i = bytes [i*B, min((i+1)*B, len)).  No empty
  *    blocks: len == 0 gives 0 blocks, and there is no trailing empty block
  *    when len % B == 0 (the reference only emits a block on ChunkInput::End
@@ -93,7 +106,8 @@ int sf_release_host_cache(void);
 /* Fixed tiling of d_data[0, len) into block_size-byte blocks; writes
  * ceil(len/block_size) digests to d_digests (20 B each).  Replaces the
  * chunk loop of src/index.rs:621-647 for fixed-size blocks.
- * SF_ENOSPC (with *n_blocks set) when cap_blocks is too small. */
+ * SF_ENOSPC (with *n_blocks set, nothing written) when cap_blocks is too
+ * small.  d_digests: 4-B aligned (each digest is five 32-bit stores). */
 int sf_index_device_fixed(const void *d_data, uint64_t len, uint32_t block_size,
                           void *d_digests, uint64_t cap_blocks, uint64_t *n_blocks,
                           void *stream);
@@ -103,7 +117,9 @@ int sf_index_device_fixed(const void *d_data, uint64_t len, uint32_t block_size,
  * in the reference), the reference KAT boundaries and ragged batches.
  * Blocks need not be sorted, aligned or disjoint.  A block outside
  * [0, len) is not read: its digest is zeroed and, if d_status != NULL,
- * *d_status (device int32, caller-initialised to 0) is set to SF_ERANGE. */
+ * *d_status (device int32, caller-initialised to 0) is set to SF_ERANGE.
+ * d_digests: 4-B aligned (digests and the zeroing are 32-bit stores);
+ * d_status: 4-B aligned. */
 int sf_index_device_blocks(const void *d_data, uint64_t len, const uint64_t *d_offsets,
                            const uint32_t *d_sizes, uint64_t n_blocks, void *d_digests,
                            int *d_status, void *stream);
@@ -113,7 +129,7 @@ int sf_index_device_blocks(const void *d_data, uint64_t len, const uint64_t *d_o
  * weak sum beside the strong hash.  As sf_index_device_fixed /
  * sf_index_device_blocks, plus d_weak[i] = zlib Adler-32 (RFC 1950) of block
  * i's bytes, fused into the same pass over HBM (uint32 per block; 0 for an
- * out-of-range explicit block). */
+ * out-of-range explicit block).  d_digests, d_weak and d_status: 4-B aligned. */
 int sf_index_device_fixed_weak(const void *d_data, uint64_t len, uint32_t block_size,
                                void *d_digests, uint32_t *d_weak, uint64_t cap_blocks,
                                uint64_t *n_blocks, void *stream);
@@ -136,7 +152,9 @@ int sf_index_device_blocks_weak(const void *d_data, uint64_t len, const uint64_t
  * lanes polled and, once, gave up).  d_status (device int32, may be NULL) is
  * accepted for source compatibility and is not written: no error of this
  * call is reported on the device.  (SF_BATCH_FUSED=0: the block kernel, then
- * a chain kernel.) */
+ * a chain kernel.)  d_digests and d_file_hashes: 4-B aligned (every route
+ * writes them as 32-bit words; a table that is also 16-B aligned takes the
+ * faster chain kernels). */
 int sf_index_device_batch(const void *d_data, uint64_t len, const sf_file_desc *files,
                           uint32_t n_files, uint32_t block_size, void *d_digests,
                           uint64_t cap_blocks, void *d_file_hashes, uint64_t *first_block,
@@ -201,7 +219,7 @@ int sf_index_device_batch_chained_cols(const void *d_data, uint32_t n_files, uin
  * d_present, one byte per row (non-zero = present; NULL = all present) --
  * then sf_block_set_lookup writes, for each of n_query digests at d_query,
  * the index of the first present row with that digest, or -1, to d_rows
- * (device int64).  Asynchronous on `stream`; n_rows <= 2^31.  Lookups only
+ * (device int64, 8-B aligned; d_query 4-B aligned).  Asynchronous on `stream`; n_rows <= 2^31.  Lookups only
  * read the set: any number may run at once, on any streams ordered after the
  * build.  sf_block_set_free releases the set (stream-ordered: after the
  * lookups on that stream). */
@@ -217,7 +235,8 @@ int sf_block_set_free(sf_block_set *set, void *stream);
  * decimal block size + "\n" (write_message, src/sync/ssh/proto.rs:162-166),
  * what FsSource sends per block after FILE_START (src/sync/fs.rs:217-233).
  * Fixed tiling of a file_len-byte file.  *n_out = bytes written (the need,
- * with SF_ENOSPC, when cap is too small). */
+ * with SF_ENOSPC and nothing written, when cap is too small).  d_out needs no
+ * alignment (byte stores). */
 int sf_wire_file_blocks_device(const void *d_digests, uint64_t n_blocks, uint32_t block_size,
                                uint64_t file_len, void *d_out, uint64_t cap, uint64_t *n_out,
                                void *stream);
@@ -227,8 +246,9 @@ int sf_wire_file_blocks_device(const void *d_digests, uint64_t n_blocks, uint32_
  * "FILE_BLOCK\n" + digest i + "\n" + decimal d_sizes[i] + "\n"
  * (src/sync/ssh/proto.rs:162-166), back to back in list order.  The message
  * offsets come from a scan on the device; the total is read back, so the call
- * blocks until it is known.  *n_out = bytes (the need); SF_ENOSPC when cap is
- * too small or d_out is NULL (a query). */
+ * blocks until it is known.  *n_out = bytes (the need); SF_ENOSPC (nothing
+ * written) when cap is too small or d_out is NULL (a query).  d_out needs no
+ * alignment (byte stores). */
 int sf_wire_blocks_device(const void *d_digests, const uint32_t *d_sizes, uint64_t n_blocks,
                           void *d_out, uint64_t cap, uint64_t *n_out, void *stream);
 
@@ -278,6 +298,7 @@ enum {
  * point: a size above 2^32 - 1 gives SF_ERANGE.  SF_ENOSPC with *n_out = the
  * need (the first cap entries written) when cap is too small or an output is
  * NULL (a query).  n_bytes == 0 gives 0 messages; n_bytes <= 2^38.
+ * d_digests and d_sizes: 4-B aligned.
  * Scratch: n_bytes / 3 from the library's stream-ordered pool.  Blocking. */
 int sf_wire_parse_blocks_device(const void *d_wire, uint64_t n_bytes, void *d_digests /* 4-B aligned */,
                                 uint32_t *d_sizes, uint64_t cap, uint64_t *n_out,
@@ -292,7 +313,9 @@ int sf_wire_parse_blocks_device(const void *d_wire, uint64_t n_bytes, void *d_di
  * set_file_size_and_compute_blocks_hash (fs.rs:480), and the base_offset of
  * the next call when a run arrives in pieces (the unconsumed tail + the new
  * bytes).  cap entries per output; SF_ENOSPC with *n_out = the need when it
- * is smaller or an output is NULL.  Blocking. */
+ * is smaller or an output is NULL (the first cap digests and sizes written,
+ * no offset and no row).  d_digests and d_sizes: 4-B aligned; d_offsets and
+ * d_rows: 8-B aligned.  Blocking. */
 int sf_receive_blocks_device(const sf_block_set *set /* NULL: no lookup */, const void *d_wire, uint64_t n_bytes,
                              uint64_t base_offset, void *d_digests, uint32_t *d_sizes, uint64_t *d_offsets,
                              int64_t *d_rows, uint64_t cap, uint64_t *n_out, uint64_t *consumed, int *stop,
@@ -346,7 +369,8 @@ int sf_receive_blocks_buffer(const sf_block_set *set, const void *wire /* host *
  * SF_ERANGE.  SF_ENOSPC with *n_out = the need (the first cap entries
  * written, nothing hashed) when cap is too small or one of d_digests,
  * d_sizes, d_data_offsets is NULL (a query).  n_bytes == 0 gives 0 messages
- * and launches nothing; n_bytes <= 2^38.  Blocking. */
+ * and launches nothing; n_bytes <= 2^38.  d_digests and d_sizes: 4-B aligned;
+ * d_data_offsets: 8-B aligned; d_ok: bytes, any address.  Blocking. */
 int sf_receive_block_data_device(const void *d_wire, uint64_t n_bytes, void *d_digests /* 4-B aligned */,
                                  uint32_t *d_sizes, uint64_t *d_data_offsets,
                                  uint8_t *d_ok /* NULL: parse only */, uint64_t cap,
@@ -398,8 +422,8 @@ int sf_receive_block_data_buffer(const void *wire /* host */, uint64_t n_bytes, 
  * allocates 256 bytes of counters that are kept (sf_test_copy_stats reads
  * them).  n_blocks == 0 launches nothing.
  * SF_EINVAL, before any device call, for a NULL list or buffer with
- * n_blocks > 0, for n_blocks > 2^32, and when [d_src, +src_len) and
- * [d_dst, +dst_len) overlap. */
+ * n_blocks > 0, for n_blocks > 2^32, when [d_src, +src_len) and
+ * [d_dst, +dst_len) overlap, and for a d_status that is not 4-B aligned. */
 int sf_copy_blocks_device(const void *d_src, uint64_t src_len, void *d_dst, uint64_t dst_len,
                           const uint64_t *d_src_offsets, const uint64_t *d_dst_offsets,
                           const uint32_t *d_sizes, const uint8_t *d_take /* NULL: all */,
@@ -418,7 +442,8 @@ int sf_write_device_fd(const void *d_data, uint64_t len, int fd, uint64_t file_o
                        uint64_t *n_written, void *stream);
 
 /* Deterministic synthetic input (bench / tests): bytes [start, start+len)
- * of the splitmix64 stream with this seed. */
+ * of the splitmix64 stream with this seed.  d_out needs no
+ * alignment (16-B stores when d_out and start are 16-B aligned, else bytes). */
 int sf_fill_splitmix_device(void *d_out, uint64_t len, uint64_t seed, uint64_t start, void *stream);
 
 /* ------------------------------------------------ host-memory entries */
@@ -686,7 +711,8 @@ int sf_zpaq_chunker_ops(uint32_t bits, uint32_t max_size, sf_chunker_ops *out);
  * lane -- still exact.  d_data needs no alignment.  *n_blocks = the count;
  * SF_ENOSPC (nothing written) when cap_blocks is smaller or an output is NULL.
  * len == 0 gives 0 blocks.  SF_EINVAL unless 1 <= bits <= 31 and
- * 16 <= max_size <= 1048576 (the device range).  Scratch: len / 4 bytes plus
+ * 16 <= max_size <= 1048576 (the device range).  d_offsets: 8-B aligned;
+ * d_sizes: 4-B aligned.  Scratch: len / 4 bytes plus
  * 56 bytes per segment, from the library's stream-ordered pool. */
 int sf_cut_device_zpaq(const void *d_data, uint64_t len, uint32_t bits, uint32_t max_size,
                        uint64_t *d_offsets, uint32_t *d_sizes, uint64_t cap_blocks,
@@ -697,7 +723,8 @@ int sf_cut_device_zpaq(const void *d_data, uint64_t len, uint32_t bits, uint32_t
  * (sf_index_device_blocks) into d_digests (cap_blocks x 20 B), then, if
  * blocks_hash (a HOST pointer, may be NULL) is given, the digests are copied
  * back and chained on the host (compute_blocks_hash, src/index.rs:661-682).
- * Blocking as sf_cut_device_zpaq; errors as there. */
+ * d_digests: 4-B aligned (32-bit stores); with SF_ENOSPC no digest is written
+ * either.  Blocking as sf_cut_device_zpaq; errors as there. */
 int sf_index_device_zpaq(const void *d_data, uint64_t len, uint32_t bits, uint32_t max_size,
                          uint64_t *d_offsets, uint32_t *d_sizes, void *d_digests, uint64_t cap_blocks,
                          uint64_t *n_blocks, uint8_t *blocks_hash, void *stream);

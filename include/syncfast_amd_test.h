@@ -35,7 +35,8 @@ int sf_test_get_stat(const char* name, int64_t* value);
  * d_order[0, n) (device uint32) receives the block indices ordered by
  * length class (4 mantissa bits, 8-bit key), descending, list order within
  * a class -- the counting sort of sf_sort.hip.  d_sizes: n device uint32.
- * Asynchronous on `stream`; SF_EINVAL for n >= 2^32. */
+ * Asynchronous on `stream`; SF_EINVAL for n >= 2^32 or a d_order that is not
+ * 4-B aligned. */
 int sf_test_table_order(const uint32_t* d_sizes, uint64_t n, uint32_t* d_order, void* stream);
 
 /* The same with `mbits` mantissa bits (1..6) of the length class: the key

@@ -321,6 +321,7 @@ int sf_index_device_fixed(const void* d_data, uint64_t len, uint32_t block_size,
                           uint64_t cap_blocks, uint64_t* n_blocks, void* stream) {
   int rc = check_fixed_args(len, block_size);
   if (rc) return rc;
+  if (misaligned(d_digests, 4)) return SF_EINVAL;  // digests are written as dwords (Sha1::store)
   const uint64_t nb = len ? ceil_div(len, block_size) : 0;
   if (n_blocks) *n_blocks = nb;
   if (nb > cap_blocks) return SF_ENOSPC;
@@ -334,6 +335,8 @@ int sf_index_device_blocks(const void* d_data, uint64_t len, const uint64_t* d_o
   // d_data may be NULL only when len == 0 (then every in-range block is
   // empty and the kernel dereferences nothing).
   if (!d_offsets || !d_sizes || !d_digests || (!d_data && len)) return SF_EINVAL;
+  // digests are written, and an out-of-range block's zeroed, as dwords
+  if (misaligned(d_digests, 4) || misaligned(d_status, 4)) return SF_EINVAL;
   return launch_table(d_data, len, d_offsets, d_sizes, n_blocks, d_digests, d_status, as_stream(stream));
 }
 
@@ -341,6 +344,7 @@ int sf_index_device_fixed_weak(const void* d_data, uint64_t len, uint32_t block_
                                uint32_t* d_weak, uint64_t cap_blocks, uint64_t* n_blocks, void* stream) {
   int rc = check_fixed_args(len, block_size);
   if (rc) return rc;
+  if (misaligned(d_digests, 4) || misaligned(d_weak, 4)) return SF_EINVAL;
   const uint64_t nb = len ? ceil_div(len, block_size) : 0;
   if (n_blocks) *n_blocks = nb;
   if (nb > cap_blocks) return SF_ENOSPC;
@@ -352,6 +356,7 @@ int sf_index_device_blocks_weak(const void* d_data, uint64_t len, const uint64_t
                                 uint64_t n_blocks, void* d_digests, uint32_t* d_weak, int* d_status, void* stream) {
   if (n_blocks == 0) return SF_OK;
   if (!d_offsets || !d_sizes || !d_digests || !d_weak || (!d_data && len)) return SF_EINVAL;
+  if (misaligned(d_digests, 4) || misaligned(d_weak, 4) || misaligned(d_status, 4)) return SF_EINVAL;
   return launch_table(d_data, len, d_offsets, d_sizes, n_blocks, d_digests, d_status, as_stream(stream), d_weak);
 }
 
@@ -361,6 +366,9 @@ static int sf_index_device_batch_body(const void* d_data, uint64_t len, const sf
   int rc = check_fixed_args(len, block_size);
   if (rc) return rc;
   if (n_files && !files) return SF_EINVAL;
+  // digests and blocks_hashes are written as dwords by every route below
+  // (d_status is never written: it needs none)
+  if (misaligned(d_digests, 4) || misaligned(d_file_hashes, 4)) return SF_EINVAL;
   hipStream_t s = as_stream(stream);
   // Plan: per-file block ranges (host, O(n_files)).
   std::vector<uint64_t> fb(n_files + 1);

@@ -443,6 +443,7 @@ int cut_device(const void* d_data, uint64_t len, uint32_t bits, uint32_t max_siz
                uint32_t* d_sizes, uint64_t cap_blocks, uint64_t* n_blocks, hipStream_t s) {
   if (n_blocks) *n_blocks = 0;
   if (!n_blocks || zpaq_check_device_params(bits, max_size) != SF_OK) return SF_EINVAL;
+  if (misaligned(d_offsets, 8) || misaligned(d_sizes, 4)) return SF_EINVAL;  // zpaq_emit_kernel's stores
   if (len == 0) return SF_OK;
   if (!d_data) return SF_EINVAL;
   PlanGuard g{{}, s};
@@ -565,6 +566,10 @@ int sf_index_device_zpaq(const void* d_data, uint64_t len, uint32_t bits, uint32
                          uint8_t* blocks_hash, void* stream) {
   return guarded([&]() -> int {
     hipStream_t s = as_stream(stream);
+    if (misaligned(d_digests, 4)) {  // digests are written as dwords (Sha1::store)
+      if (n_blocks) *n_blocks = 0;
+      return SF_EINVAL;
+    }
     int rc = cut_device(d_data, len, bits, max_size, d_offsets, d_sizes, cap_blocks, n_blocks, s);
     if (rc != SF_OK) return rc;
     const uint64_t n = *n_blocks;

@@ -201,6 +201,7 @@ int copy_blocks(const uint8_t* d_src, uint64_t src_len, uint8_t* d_dst, uint64_t
   g_copy_dev.store(-1, std::memory_order_relaxed);
   if (n == 0) return SF_OK;
   if (!d_src || !d_dst || !d_src_off || !d_dst_off || !d_sizes || n > kMaxJobs) return SF_EINVAL;
+  if (misaligned(d_status, 4)) return SF_EINVAL;  // written as one int
   const uint64_t a = reinterpret_cast<uint64_t>(d_src), b = reinterpret_cast<uint64_t>(d_dst);
   if (src_len && dst_len && a < b + dst_len && b < a + src_len) return SF_EINVAL;  // the buffers overlap
 

@@ -120,6 +120,12 @@ inline void clear_stale_error() { (void)hipGetLastError(); }
 
 inline uint64_t ceil_div(uint64_t a, uint64_t b) { return (a + b - 1) / b; }
 
+// Whether an output pointer breaks the alignment include/syncfast_amd.h states
+// for it (a power of two: the widest store a kernel makes to it -- digests and
+// hashes are five dword stores, Sha1::store).  NULL is aligned.  The entry
+// points refuse such a pointer with SF_EINVAL before any device call.
+inline bool misaligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
+
 inline int check_fixed_args(uint64_t len, uint32_t bs) {
   if (bs == 0 || bs > SF_MAX_BLOCK_SIZE) return SF_EINVAL;
   (void)len;

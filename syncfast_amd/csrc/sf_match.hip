@@ -159,6 +159,7 @@ int sf_block_set_lookup(const sf_block_set* set, const void* d_query, uint64_t n
                         void* stream) {
   if (!set || (n_query && (!d_query || !d_rows))) return SF_EINVAL;
   if (reinterpret_cast<uintptr_t>(d_query) & 3u) return SF_EINVAL;
+  if (misaligned(d_rows, 8)) return SF_EINVAL;  // one 8-B store per query
   const uint64_t per = 1ull << 31;  // queries per launch (< 2^32 work-items)
   for (uint64_t q0 = 0; q0 < n_query; q0 += per) {
     const uint64_t nq = std::min(per, n_query - q0);

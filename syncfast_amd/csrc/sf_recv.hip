@@ -241,7 +241,7 @@ int parse_blocks_device(const void* d_wire, uint64_t n_bytes, void* d_digests, u
   if (consumed) *consumed = 0;
   if (stop) *stop = SF_WIRE_END;
   if (!n_out || !consumed || !stop || (n_bytes && !d_wire) || n_bytes > kMaxRun ||
-      (reinterpret_cast<uintptr_t>(d_digests) & 3u))
+      misaligned(d_digests, 4) || misaligned(d_sizes, 4))
     return SF_EINVAL;
   if (n_bytes == 0) return SF_OK;
   if (!d_digests || !d_sizes) cap = 0;
@@ -379,8 +379,11 @@ int sf_receive_blocks_device(const sf_block_set* set, const void* d_wire, uint64
   return guarded([&]() -> int {
     const ReceiveArgs a{set, base_offset, d_digests, d_sizes, d_offsets, d_rows, cap, n_out, consumed, stop, end_offset};
     const int rc = check_receive_args(a, d_wire, n_bytes);
-    if (rc != SF_OK || n_bytes == 0) return rc;
-    if (reinterpret_cast<uintptr_t>(d_digests) & 3u) return SF_EINVAL;
+    if (rc != SF_OK) return rc;
+    // dword stores to the digests and sizes, 8-B stores to the offsets (the scan) and rows
+    if (misaligned(d_digests, 4) || misaligned(d_sizes, 4) || misaligned(d_offsets, 8) || misaligned(d_rows, 8))
+      return SF_EINVAL;
+    if (n_bytes == 0) return SF_OK;
     return receive_device(a, static_cast<const uint8_t*>(d_wire), nullptr, n_bytes, as_stream(stream), nullptr);
   });
 }

@@ -455,7 +455,8 @@ int sf_receive_block_data_device(const void* d_wire, uint64_t n_bytes, void* d_d
     const Results r{n_out, consumed, stop, need, n_bad};
     const int rc = check_args(r, d_wire, n_bytes);
     if (rc != SF_OK) return rc;
-    if (reinterpret_cast<uintptr_t>(d_digests) & 3u) return SF_EINVAL;
+    // dword stores to the digests and sizes, 8-B stores to the offsets; d_ok is bytes
+    if (misaligned(d_digests, 4) || misaligned(d_sizes, 4) || misaligned(d_data_offsets, 8)) return SF_EINVAL;
     if (n_bytes == 0) return SF_OK;
     if (!d_digests || !d_sizes || !d_data_offsets) cap = 0;  // a query
     const Provide provide = [&](uint64_t, Outputs* o) -> int {  // the caller's, whatever the count

@@ -208,7 +208,7 @@ extern "C" int sf_test_table_order_bits(const uint32_t* d_sizes, uint64_t n, uin
                                         void* stream) {
   if (mbits < 1 || mbits > 6) return SF_EINVAL;
   if (n == 0) return SF_OK;
-  if (!d_sizes || !d_order || n > 0xFFFFFFFFull) return SF_EINVAL;
+  if (!d_sizes || !d_order || n > 0xFFFFFFFFull || sfi::misaligned(d_order, 4)) return SF_EINVAL;
   hipStream_t s = static_cast<hipStream_t>(stream);
   void* ws = nullptr;
   const uint32_t kmax = (16u << (mbits < 4 ? 4 : mbits)) - 1u;

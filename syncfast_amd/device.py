@@ -76,14 +76,18 @@ def _ptr(t: Optional[torch.Tensor], n: Optional[int] = None) -> Optional[int]:
 
 def _out(out: Optional[torch.Tensor], name: str, shape: tuple, dtype, data: torch.Tensor) -> torch.Tensor:
     """An output of ``shape`` on the input's device: a new tensor, or the
-    caller's once it is seen to be there, of that dtype, contiguous and large
-    enough.  Call inside ``_on``: the allocation belongs to the launch stream."""
+    caller's once it is seen to be there, of that dtype, contiguous, large
+    enough and 4-byte aligned (digest tables, hashes and weak sums are written
+    as 32-bit words: include/syncfast_amd.h; a uint8 view may start anywhere).
+    Call inside ``_on``: the allocation belongs to the launch stream."""
     if out is None:
         return torch.empty(shape, dtype=dtype, device=data.device)
     _require_device(out, name, dtype, data.device)
     need = math.prod(shape)
     if out.numel() < need:
         raise ValueError(f"{name} holds {out.numel()} elements, need {need}")
+    if out.data_ptr() % 4:
+        raise ValueError(f"{name} must start 4-byte aligned (it starts {out.data_ptr() % 4} bytes past)")
     return out
 
 

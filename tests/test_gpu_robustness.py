@@ -161,9 +161,11 @@ def test_wide_batch(gpu):
 
 
 def test_unaligned_outputs(gpu):
-    # a hashes_out 20 B into a larger tensor (any alignment is fine for the
-    # hashes) and a digest table 4 B off a 16-B boundary (file runs not 16-B
-    # aligned: blocks then the per-lane chain kernel); same hashes
+    # a hashes_out 20 B into a larger tensor (the hashes need 4-B alignment,
+    # as every digest table does: they are written as 32-bit words, and any
+    # other address is SF_EINVAL; include/syncfast_amd.h) and a digest table
+    # 4 B off a 16-B boundary (file runs not 16-B aligned: blocks then the
+    # per-lane chain kernel); same hashes
     data, t, files = _equal_batch(gpu, 70, 1024, 4096, 505)
     buf = torch.empty((71, 20), dtype=torch.uint8, device=gpu)
     fh = buf[1:]

@@ -136,6 +136,61 @@ def test_blocks_device_validation_without_device():
     assert L.sf_wire_blocks_fd(None, None, 3, 1, ctypes.byref(n), None) == _lib.SF_EINVAL
 
 
+def test_output_alignment_is_checked_without_device():
+    """Every device output has the alignment include/syncfast_amd.h states for
+    it, and a pointer that breaks it is SF_EINVAL before any device call: the
+    addresses here are made up and nothing may touch them.  One byte off and,
+    where the rule is 8 bytes, four bytes off.  A capacity query with aligned
+    pointers still answers SF_ENOSPC with the need."""
+    from syncfast_amd import _lib
+    L, EINVAL, ENOSPC = _lib.lib(), _lib.SF_EINVAL, _lib.SF_ENOSPC
+    IN, IN2, IN3, OUT = 0x10000, 0x20000, 0x30000, 0x40000  # inputs; the base of the outputs
+    n, used, end, need, bad = (ctypes.c_uint64(7) for _ in range(5))
+    stop = ctypes.c_int(0)
+    R = ctypes.byref
+    descs = (_lib.FileDesc * 1)(_lib.FileDesc(0, 640))
+    first = (ctypes.c_uint64 * 2)()
+
+    # name -> (call(*outputs), the rule of each output)
+    calls = {
+        "fixed": (lambda d: L.sf_index_device_fixed(IN, 640, 64, d, 10, R(n), None), [4]),
+        "fixed_weak": (lambda d, w: L.sf_index_device_fixed_weak(IN, 640, 64, d, w, 10, R(n), None), [4, 4]),
+        "blocks": (lambda d, s: L.sf_index_device_blocks(IN, 640, IN2, IN3, 3, d, s, None), [4, 4]),
+        "blocks_weak": (lambda d, w, s: L.sf_index_device_blocks_weak(IN, 640, IN2, IN3, 3, d, w, s, None), [4, 4, 4]),
+        "batch": (lambda d, h: L.sf_index_device_batch(IN, 640, descs, 1, 64, d, 10, h, first, R(n), None, None), [4, 4]),
+        "lookup": (lambda r: L.sf_block_set_lookup(IN2, IN, 3, r, None), [8]),
+        "parse": (lambda d, z: L.sf_wire_parse_blocks_device(IN, 100, d, z, 3, R(n), R(used), R(stop), None), [4, 4]),
+        "receive": (lambda d, z, o, r: L.sf_receive_blocks_device(None, IN, 100, 0, d, z, o, r, 3, R(n), R(used),
+                                                                   R(stop), R(end), None), [4, 4, 8, 8]),
+        "block_data": (lambda d, z, o: L.sf_receive_block_data_device(IN, 100, d, z, o, None, 3, R(n), R(used), R(stop),
+                                                                      R(need), R(bad), None), [4, 4, 8]),
+        "cut_zpaq": (lambda o, z: L.sf_cut_device_zpaq(IN, 20000, 6, 256, o, z, 400, R(n), None), [8, 4]),
+        "index_zpaq": (lambda o, z, d: L.sf_index_device_zpaq(IN, 20000, 6, 256, o, z, d, 400, R(n), None, None),
+                       [8, 4, 4]),
+        "table_order": (lambda o: L.sf_test_table_order(IN, 100, o, None), [4]),
+        "copy_status": (lambda s: L.sf_copy_blocks_device(IN, 100, IN2, 100, IN3, IN3 + 0x1000, IN3 + 0x2000, None, 3, s,
+                                                          None), [4]),
+    }
+    for name, (call, rules) in calls.items():
+        good = [OUT + 0x1000 * k for k in range(len(rules))]
+        for k, rule in enumerate(rules):
+            for off in (1, 4) if rule == 8 else (1,):
+                outs = list(good)
+                outs[k] += off
+                assert call(*outs) == EINVAL, (name, k, off)
+
+    # the capacity queries that need no device: aligned pointers, cap too small
+    n.value = 0
+    assert L.sf_index_device_fixed(IN, 640, 64, OUT, 9, R(n), None) == ENOSPC and n.value == 10
+    n.value = 0
+    assert L.sf_index_device_fixed_weak(IN, 640, 64, OUT, OUT + 0x1000, 9, R(n), None) == ENOSPC and n.value == 10
+    n.value = 0
+    assert L.sf_index_device_batch(IN, 640, descs, 1, 64, OUT, 9, OUT + 0x1000, first, R(n), None, None) == ENOSPC
+    assert n.value == 10 and list(first) == [0, 10]
+    # wire bytes need no alignment: an odd d_out is no error
+    assert L.sf_wire_file_blocks_device(IN, 10, 64, 640, OUT + 1, 349, R(n), None) == ENOSPC and n.value == 350
+
+
 @pytest.mark.gpu
 def test_blocks_device_reference_kat_blocks(gpu):
     """The KAT file's three content-defined blocks (src/index.rs:765-792) as
