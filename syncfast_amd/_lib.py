@@ -349,10 +349,11 @@ def kernel_code_sha256(path: str = None, symbol: str = FIXED_KERNEL) -> str:
 def code_object_sha256(path: str = None, kernel: bytes = b"sha1_fixed_kernel") -> str:
     """SHA-256 of the gfx950 code object that holds `kernel` (the library's
     ``.hip_fatbin`` section holds one clang offload bundle per GPU translation
-    unit; the SHA-1 kernels are in sf_capi.hip's).  What the GPU runs for that
-    kernel: host-only changes, and changes to other translation units' kernels,
-    leave it unchanged; any change to the SHA-1 kernels alters it.  bench.py
-    keys the PMC traffic of profiles/traffic.json on it."""
+    unit; sha1_fixed_kernel is in sf_capi.hip's, with the stand-alone chain
+    kernel and the splitmix fill).  Host-only changes, and changes to other
+    translation units' kernels, leave it unchanged; any change to a kernel of
+    that unit alters it.  bench.py reports it; nothing is matched on it (the
+    PMC traffic of profiles/traffic.json is keyed on kernel_code_sha256)."""
     import hashlib
     for _, co in _code_objects(path):
         if kernel in co:

@@ -59,7 +59,7 @@
 #include <memory>
 
 #include "host_sha1.h"
-#include "sf_internal.hpp"
+#include "sf_launch.hpp"
 #include "sf_stage.hpp"
 #include "sf_zpaq_step.hpp"
 #include "../../include/syncfast_amd_test.h"

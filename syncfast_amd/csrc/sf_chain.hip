@@ -1,12 +1,14 @@
 // sf_chain.hip -- blocks_hash chains alone on the device (a stream's finish
-// launches): sha1_chain_helper_kernel.
+// launches): sha1_chain_helper_kernel, alone in its
+// code object.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "sf_chain.hpp"
-#include "sf_internal.hpp"
+#include "sf_block_hash.hpp"
 
 namespace sf {
+
+constexpr int kChainDepth = 4;  // 64-B chunks the helper wave keeps in flight per lane
 
 // A stream's chain jobs on an otherwise idle GPU (BatchStream's finish
 // launches, sf_index_device_batch_chained_cols with no blocks).  A lone chain
@@ -71,13 +73,7 @@ sha1_chain_helper_kernel(const ChainJob j0, const ChainJob j1) {
         if (c < n) {
           uint32_t w[16];
           if (c < n_data) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-              w[4 * i + 0] = bswap32(buf[k][i].x);
-              w[4 * i + 1] = bswap32(buf[k][i].y);
-              w[4 * i + 2] = bswap32(buf[k][i].z);
-              w[4 * i + 3] = bswap32(buf[k][i].w);
-            }
+            be_words(w, buf[k]);
             const uint32_t nx = c + D < n_data ? c + D : n_data - 1;
 #pragma unroll
             for (int i = 0; i < 4; ++i) buf[k][i] = q[(uint64_t)nx * 4 + i];

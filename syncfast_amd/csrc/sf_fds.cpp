@@ -29,7 +29,7 @@
 #include <vector>
 
 #include "host_sha1.h"
-#include "sf_internal.hpp"
+#include "sf_launch.hpp"
 #include "sf_stage.hpp"
 
 using namespace sfi;

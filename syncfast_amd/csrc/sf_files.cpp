@@ -71,7 +71,7 @@ extern "C" {
 static int sf_index_files_body(const char* const* paths, uint32_t n_files, uint32_t block_size, uint64_t stage_bytes_hint,
                    sf_block_sig* out, uint64_t cap, uint64_t* first_row, uint8_t* blocks_hashes, uint64_t* n_out,
                    uint32_t* bad_file) {
-  int rc = check_fixed_args(0, block_size);
+  int rc = check_block_size(block_size);
   if (rc) return rc;
   if (n_files && (!paths || !first_row || !blocks_hashes)) return SF_EINVAL;
   const uint32_t bs = block_size;

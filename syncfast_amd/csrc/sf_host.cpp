@@ -1,6 +1,6 @@
 // sf_host.cpp -- the C-ABI's host-memory entry points (include/syncfast_amd.h):
 // bytes in host memory, in a file or behind a descriptor -> pinned stages ->
-// H2D -> the gfx950 kernels (launched through sf_capi.hip) -> D2H of the rows,
+// H2D -> the gfx950 kernels (launched through sf_launch.hpp) -> D2H of the rows,
 // plus the per-device cache of streams and buffers these calls share, the
 // streamed FILE_BLOCK run and the host SHA-1 helpers.  HIP runtime API only:
 // built with the host compiler.
@@ -23,7 +23,7 @@
 #include <vector>
 
 #include "host_sha1.h"
-#include "sf_internal.hpp"
+#include "sf_launch.hpp"
 #include "sf_stage.hpp"
 
 namespace sfi __attribute__((visibility("hidden"))) {
@@ -929,7 +929,7 @@ static int sf_index_fd_blocks_body(int fd, const sf_file_stamp* expect, const ui
 static int sf_index_fd_fixed_body(int fd, const sf_file_stamp* expect, uint32_t block_size, sf_block_sig* out,
                                   uint64_t cap, uint64_t* n_out, uint8_t* blocks_hash) {
   if (n_out) *n_out = 0;
-  int rc = check_fixed_args(0, block_size);
+  int rc = check_block_size(block_size);
   if (rc) return rc;
   if (fd < 0) return SF_EINVAL;
   return stamped(fd, expect, [&](const sf_file_stamp& st, mode_t mode) {
@@ -953,7 +953,7 @@ int sf_file_stamp_fd(int fd, sf_file_stamp* out) {
 
 static int sf_index_buffer_body(const uint8_t* data, uint64_t len, uint32_t block_size, sf_block_sig* out, uint64_t cap,
                     uint64_t* n_out) {
-  int rc = check_fixed_args(len, block_size);
+  int rc = check_block_size(block_size);
   if (rc) return rc;
   if (len && (!data || !out)) return SF_EINVAL;
   // Large buffers of private anonymous memory: page-locked in place (no
@@ -982,7 +982,7 @@ static int sf_index_buffer_body(const uint8_t* data, uint64_t len, uint32_t bloc
 
 static int sf_index_file_body(const char* path, uint32_t block_size, sf_block_sig* out, uint64_t cap, uint64_t* n_out,
                   uint8_t blocks_hash[20]) {
-  int rc = check_fixed_args(0, block_size);
+  int rc = check_block_size(block_size);
   if (rc) return rc;
   if (!path) return SF_EINVAL;
   const int fd = open(path, O_RDONLY);
@@ -1031,7 +1031,7 @@ static int sf_index_file_body(const char* path, uint32_t block_size, sf_block_si
 
 static int sf_index_file_range_body(const char* path, uint64_t start, uint64_t len, uint32_t block_size, sf_block_sig* out,
                         uint64_t cap, uint64_t* n_out) {
-  int rc = check_fixed_args(0, block_size);
+  int rc = check_block_size(block_size);
   if (rc) return rc;
   if (!path || (len && start % block_size)) return SF_EINVAL;  // an empty shard may start anywhere up to EOF
   const uint64_t nb = len ? ceil_div(len, block_size) : 0;
@@ -1051,7 +1051,7 @@ static int sf_index_file_range_body(const char* path, uint64_t start, uint64_t l
 static int sf_index_fd_body(int fd, uint32_t block_size, sf_block_sig** rows, uint64_t* n_out, uint8_t blocks_hash[20]) {
   if (rows) *rows = nullptr;
   if (n_out) *n_out = 0;
-  int rc = check_fixed_args(0, block_size);
+  int rc = check_block_size(block_size);
   if (rc) return rc;
   if (fd < 0 || !rows || !n_out) return SF_EINVAL;
   RowBuf rb;

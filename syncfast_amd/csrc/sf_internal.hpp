@@ -1,8 +1,22 @@
 // sf_internal.hpp -- library-internal declarations shared by the C-ABI's
-// translation units (not part of include/syncfast_amd.h):
-//   sf_capi.hip   the gfx950 kernels' launchers and the device-resident entry
-//                 points (the only TU compiled for the GPU);
-//   sf_host.cpp   the host-memory entry points: per-device cache of streams
+// translation units (not part of include/syncfast_amd.h).  The .hip files are
+// compiled for the GPU, each into a code object of its own; the SHA-1 block
+// kernels share the wave functions of sf_block_hash.hpp and are launched
+// through sf_launch.hpp:
+//   sf_capi.hip   sha1_fixed_kernel (the headline), the stand-alone chain
+//                 kernel, the splitmix fill and the simple device-resident
+//                 entry points;
+//   sf_stream.hip sha1_fixed_chained_kernel: a batch's blocks beside the
+//                 blocks_hash chains of earlier batches;
+//   sf_chain.hip  sha1_chain_helper_kernel: chains alone, with helper waves;
+//   sf_table.hip  sha1_table_kernel: explicit block lists, and how a list is
+//                 launched;
+//   sf_sort.hip   the counting sort that orders a list by length class;
+//   sf_wire.hip   FILE_BLOCK runs written on the device;
+//   sf_match.hip  digest lookup; sf_litmus.hip  a memory-model probe;
+//   sf_batch.cpp  the device-resident batch entry points (host planning over
+//                 the launchers);
+//   sf_host.cpp  the host-memory entry points: per-device cache of streams
 //                 and staging buffers, the buffer / file / fd / range
 //                 pipelines, the wire stream, host SHA-1 helpers;
 //   sf_files.cpp  sf_index_files, the many-file pipeline;
@@ -126,19 +140,9 @@ inline uint64_t ceil_div(uint64_t a, uint64_t b) { return (a + b - 1) / b; }
 // points refuse such a pointer with SF_EINVAL before any device call.
 inline bool misaligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
 
-inline int check_fixed_args(uint64_t len, uint32_t bs) {
-  if (bs == 0 || bs > SF_MAX_BLOCK_SIZE) return SF_EINVAL;
-  (void)len;
-  return SF_OK;
-}
+// A fixed tiling's block size: 1 .. SF_MAX_BLOCK_SIZE.
+inline int check_block_size(uint32_t bs) { return bs == 0 || bs > SF_MAX_BLOCK_SIZE ? SF_EINVAL : SF_OK; }
 
-// Launchers of the gfx950 kernels (sf_capi.hip).
-int launch_fixed(const void* d_data, uint64_t len, uint32_t bs, uint64_t nblocks, void* d_digests,
-                 hipStream_t stream, uint32_t* weak = nullptr);
-// Explicit block list (sha1_table_kernel; sorted by length class from 65
-// blocks).  d_status may be NULL.
-int launch_table(const void* d_data, uint64_t len, const uint64_t* d_offsets, const uint32_t* d_sizes,
-                 uint64_t nblocks, void* d_digests, int* d_status, hipStream_t stream, uint32_t* weak = nullptr);
 // Stream-ordered scratch (sf_alloc.cpp): allocated, used and freed on one
 // stream, from the library's pool of the stream's device, whose blocks are
 // reused on the freeing stream only.  stream_alloc returns an SF_ code.
@@ -155,8 +159,6 @@ struct Scratch {
 };
 // The parts of one allocation start on 256-byte boundaries.
 inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-int launch_wire(const uint8_t* d_digests, uint64_t n, uint32_t bs, uint32_t last, uint8_t* d_out,
-                hipStream_t stream);
 // FILE_BLOCK runs of explicit lists (sf_wire.hip): end offsets of every
 // message (stream-ordered allocation, hipFreeAsync on s), the end offset of
 // every chunk of `per` messages, and messages [first, first + cnt) written
@@ -310,12 +312,6 @@ inline unsigned io_threads() {
 size_t class_order_workspace(uint64_t n, uint32_t kmax);
 int class_order(const uint32_t* d_sizes, uint64_t n, uint32_t mbits, uint32_t kmax, void* d_ws, uint32_t* d_order,
                 hipStream_t s);
-// sha1_table_kernel<128, weak_form> on `stream` (sf_table.hip, its own
-// translation unit), one group of 64 blocks per wave; SF_OK or the launch
-// error.
-int launch_table_kernel(bool weak_form, const uint8_t* d_data, uint64_t len, const uint64_t* d_offsets,
-                        const uint32_t* d_sizes, uint64_t nblocks, uint8_t* d_digests, int* d_status, uint32_t* weak,
-                        const uint32_t* order, hipStream_t stream);
 
 // The device ZPAQ cutter (sf_cdc.hip): a plan is the cut of one buffer up to
 // its block count (blocking: a synchronisation per join round and one for the

@@ -30,7 +30,7 @@
 #include <rccl/rccl.h>
 
 #include "host_sha1.h"
-#include "sf_internal.hpp"
+#include "sf_launch.hpp"
 #include "../../include/syncfast_amd_test.h"
 
 using namespace sfi;
@@ -131,7 +131,7 @@ int sf_shard_range(uint64_t file_len, uint32_t block_size, uint32_t n_shards, ui
 static int sf_index_file_multi_body(const char* path, uint32_t block_size, uint32_t n_devices, sf_block_sig* out,
                                     uint64_t cap, uint64_t* n_out, uint8_t* blocks_hash) {
   if (n_out) *n_out = 0;
-  int rc = check_fixed_args(0, block_size);
+  int rc = check_block_size(block_size);
   if (rc) return rc;
   if (!path || !blocks_hash) return SF_EINVAL;
   int ndev = 0;
@@ -258,7 +258,7 @@ int sf_test_multi_plan(uint64_t file_len, uint32_t block_size, uint32_t n_device
 static int sf_index_device_multi_body(uint32_t n_devices, const void* const* d_shards, uint64_t file_len,
                                       uint32_t block_size, void* const* d_digests, uint32_t root, void* d_table,
                                       void* const* streams, void* const* gather_streams) {
-  int rc = check_fixed_args(0, block_size);
+  int rc = check_block_size(block_size);
   if (rc) return rc;
   if (n_devices == 0 || n_devices > (uint32_t)kMaxDevices || root >= n_devices || !d_shards || !d_digests ||
       !d_table)

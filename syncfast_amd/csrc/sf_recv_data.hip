@@ -44,6 +44,7 @@
 
 #include <memory>
 
+#include "sf_launch.hpp"
 #include "sf_recv_scan.hpp"
 #include "sf_wire_data.hpp"
 #include "../../include/syncfast_amd_test.h"

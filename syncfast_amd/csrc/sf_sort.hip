@@ -6,17 +6,32 @@
 // spent ~45 us per call (key kernel, three buffer fills, histogram and
 // onesweep passes) on what is one pass over 256 bins.
 //
-// Its own translation unit, so that it cannot change how sf_capi.hip's
-// block kernels compile.
-#define SF_STREAM_TU 1  // the device functions of sf_kernels.hpp only
+// Its own translation unit and code object: it shares no device code with the
+// block kernels but the chunk count of sha1_device.hpp.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "sf_internal.hpp"
-#include "sf_kernels.hpp"
+#include "sha1_device.hpp"
 #include "../../include/syncfast_amd_test.h"
 
 namespace sf {
+
+// The length class of a block for sha1_table_kernel's `order`: the block's
+// compression count on a log scale with `mbits` mantissa bits (classes 6.25 %
+// wide with 4 bits, exact below 16; the key is clamped to kmax = 255, so
+// every block of >= 2^16 compressions shares the top class).  A class holds
+// many blocks, so a wave's 64 blocks (consecutive in the stable sort: list
+// order within a class) lie close together in memory; an exact-count key
+// spreads them over the whole buffer (every nch value is rare), and 64 lanes
+// streaming from 64 far-apart places run memory-bound: 4 KiB blocks in a
+// shuffled order hashed at 1200 GiB/s against 2857 in order
+// (scripts/ragged_probe.py).
+__device__ __forceinline__ uint16_t length_class(uint32_t nch, uint32_t mbits) {
+  if (nch < (1u << mbits)) return (uint16_t)nch;
+  const uint32_t e = 31u - (uint32_t)__builtin_clz(nch);  // floor(log2), >= mbits
+  return (uint16_t)((e << mbits) + ((nch >> (e - mbits)) & ((1u << mbits) - 1u)));  // < 32 << mbits
+}
 
 constexpr int kSortThreads = 256;
 // blocks per thread per tile: 1024-block tiles (2048: scatter 9.8 -> 7.7 us

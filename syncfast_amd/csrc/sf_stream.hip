@@ -4,16 +4,87 @@
 //
 // Its own translation unit: how its block part is compiled decides its rate
 // (one compiled form of the same source ran 3 % slower than the plain kernel,
-// another at its rate), so no change elsewhere may move it.  The measured
-// form's machine code is recorded in profiles/r03/c3/chained_kernel.json.
-#define SF_STREAM_TU 1  // the device functions of sf_kernels.hpp, not sf_capi.hip's kernels
+// another at its rate).  Its code object holds this kernel alone; what can
+// still move it is a change to the wave functions of sf_block_hash.hpp, which
+// it shares with the other block kernels.  The measured form's machine code is
+// recorded in profiles/r03/c3/chained_kernel.json.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "sf_internal.hpp"
-#include "sf_kernels.hpp"
+#include "sf_block_hash.hpp"
 
 namespace sf {
+
+constexpr int kChainPrio = 3;  // wave priority of the stream's chain waves
+// A stream's chain job on the chain wave of a block launch (wave 0 of one
+// of the first workgroups, sha1_fixed_chained_kernel).  Its digest loads are
+// staged through the workgroup's LDS tile (unused by a chain wave
+// otherwise), as the block waves stage theirs: per step, 8 DMA
+// wave-instructions each move whole 128-B lines of 8 files, so one
+// instruction touches 8 lines instead of the 64 that a lane-per-file load
+// touches.  The lane-per-file loads (4 chunks in flight per lane) cost the
+// launch 0.050 ms per batch of chains, the staged form 0.032 (config 3
+// launch sequence, profiles/r03/c3/seq/seq_chain_lds.txt).  Data chunks
+// [lo, hi) of each lane's run; part 0/2 then the padding chunk(s).
+__device__ __forceinline__ void chain_job(const ChainJob& j, uint32_t wave, uint4* __restrict__ tile) {
+  __builtin_amdgcn_s_setprio(kChainPrio);  // latency-bound chains issue first on a shared SIMD
+  const int lane = lane_id();
+  const uint32_t f = wave * 64 + lane;
+  const bool valid = f < j.files;
+  Sha1 st;
+  if (j.part == 2 && valid) {
+    const uint32_t* sv = reinterpret_cast<const uint32_t*>(j.state + (uint64_t)f * 20);
+    st.h0 = sv[0]; st.h1 = sv[1]; st.h2 = sv[2]; st.h3 = sv[3]; st.h4 = sv[4];
+  } else {
+    st.init();
+  }
+  const uint32_t n = j.hi - j.lo;                 // data chunks, uniform
+  const uint32_t nsteps = (n + 1) / 2;
+  const uint8_t* span_ptr = j.runs + (uint64_t)wave * 64 * j.run_len + (uint64_t)j.lo * 64;
+  const uint64_t files_here = j.files - wave * 64 < 64 ? j.files - wave * 64 : 64;
+  const uint64_t span = (files_here - 1) * j.run_len + (uint64_t)n * 64;
+  uint32_t voff[8];
+#pragma unroll
+  for (int q = 0; q < 8; ++q) {
+    const int b = q * 8 + lane / 8;  // file of the wave
+    const int s = lane % 8;
+    const int k = s ^ ((b >> 1) & 7);
+    voff[q] = (uint32_t)b * j.run_len + (uint32_t)k * 16u;
+  }
+  const int g = (lane >> 1) & 7;
+  const uint4* my = tile + lane * 8;
+  if (nsteps > 0) issue_dma<8, 128, kLoadAux>(span_ptr, span, 0, voff, tile);
+  for (uint32_t t = 0; t < nsteps; ++t) {
+    uint4 raw[8];
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#pragma unroll
+    for (int k = 0; k < 8; ++k) raw[k] = my[k ^ g];
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    if (t + 1 < nsteps) issue_dma<8, 128, kLoadAux>(span_ptr, span, t + 1, voff, tile);
+#pragma unroll
+    for (int ch = 0; ch < 2; ++ch) {
+      if (2 * t + ch < n) {
+        uint32_t w[16];
+        be_words(w, raw + 4 * ch);
+        st.compress(w);
+      }
+    }
+  }
+  if (!valid) return;
+  const uint8_t* p = j.runs + (uint64_t)f * j.run_len;
+  if (j.part == 1) {
+    uint32_t* sv = reinterpret_cast<uint32_t*>(j.state + (uint64_t)f * 20);
+    sv[0] = st.h0; sv[1] = st.h1; sv[2] = st.h2; sv[3] = st.h3; sv[4] = st.h4;
+    return;
+  }
+  const uint32_t nch = n_chunks(j.run_len);
+  for (uint32_t c = j.run_len / 64; c < nch; ++c) {
+    uint32_t w[16];
+    build_tail_chunk(w, p, j.run_len, c, nch);
+    st.compress(w);
+  }
+  st.store(j.hashes + (uint64_t)f * 20);
+}
 
 // Equal-size many-file batches as a stream (BASELINE configs[2], batch after
 // batch): ONE launch hashes every block of batch i (fixed_wave) and, in its

@@ -1,6 +1,6 @@
-// sf_wire.hip -- the FILE_BLOCK run of an explicit block list, built on the
-// device (its own translation unit: the SHA-1 kernels' code object in
-// sf_capi.hip stays as it is).
+// sf_wire.hip -- FILE_BLOCK runs built on the device, of a fixed tiling and of
+// an explicit block list (its own translation unit and code object: byte
+// stores and a rocprim scan, no SHA-1).
 //
 // The reference's source streams one FILE_BLOCK message per block after
 // FILE_START (src/sync/fs.rs:217-233, written by write_message,
@@ -9,17 +9,24 @@
 // content-defined blocks every size differs, so message i starts at the sum
 // of the earlier messages' lengths (33 + digits(size)): one pass writes the
 // lengths, a rocprim inclusive scan turns them into end offsets, and one
-// thread per message writes it at its place.
+// thread per message writes it at its place.  In a fixed tiling every block
+// is block_size bytes except the last, so message i starts at
+// i * (33 + digits(block_size)) and one kernel writes the run.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <rocprim/device/device_scan.hpp>
 
-#include "sf_internal.hpp"
+#include "sf_launch.hpp"
 
 namespace {
 
-__device__ __forceinline__ uint32_t digits10(uint32_t v) {
+// Decimal digits of v, on the device and on the host.  The division runs in
+// v's own width: the explicit-list kernels divide in 32 bits, the fixed
+// tiling's kernel widens its argument and divides in 64, which is how each
+// was compiled when its machine code was recorded.
+template <typename T>
+__host__ __device__ __forceinline__ uint32_t digits10(T v) {
   uint32_t d = 1;
   while (v >= 10) { v /= 10; ++d; }
   return d;
@@ -66,7 +73,53 @@ constexpr uint64_t kWireMaxPerLaunch = 1ull << 30;  // messages per launch (grid
 
 }  // namespace
 
+namespace sf {
+
+// The FILE_BLOCK messages of a fixed tiling.  One thread per message, byte
+// stores.
+__global__ void __launch_bounds__(256)
+wire_file_blocks_kernel(const uint8_t* __restrict__ digests, uint64_t n, uint32_t block_size, uint32_t last_size,
+                        uint8_t* __restrict__ out) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t db = digits10((uint64_t)block_size);
+  const uint64_t msg = 33 + db;  // 11 + 20 + 1 + digits + 1
+  uint8_t* o = out + i * msg;
+  const char tag[11] = {'F', 'I', 'L', 'E', '_', 'B', 'L', 'O', 'C', 'K', '\n'};
+#pragma unroll
+  for (int k = 0; k < 11; ++k) o[k] = (uint8_t)tag[k];
+  const uint8_t* d = digests + i * 20;
+#pragma unroll
+  for (int k = 0; k < 20; ++k) o[11 + k] = d[k];
+  o[31] = '\n';
+  uint32_t v = (i + 1 == n) ? last_size : block_size;
+  const uint32_t nd = digits10((uint64_t)v);
+  for (int k = (int)nd - 1; k >= 0; --k) { o[32 + k] = (uint8_t)('0' + v % 10); v /= 10; }
+  o[32 + nd] = '\n';
+}
+
+}  // namespace sf
+
 namespace sfi {
+
+int launch_wire(const uint8_t* d_digests, uint64_t n, uint32_t bs, uint32_t last, uint8_t* d_out,
+                hipStream_t stream) {
+  if (n == 0) return SF_OK;
+  const uint64_t maxb = launch_max_blocks();
+  if (n > maxb) {  // consecutive runs of messages, one launch each
+    for (uint64_t first = 0; first < n; first += maxb) {
+      const uint64_t cnt = std::min(maxb, n - first);
+      const int rc = launch_wire(d_digests + first * 20, cnt, bs, first + cnt == n ? last : bs,
+                                 d_out + first * (33 + digits10(bs)), stream);
+      if (rc) return rc;
+    }
+    return SF_OK;
+  }
+  clear_stale_error();
+  hipLaunchKernelGGL(sf::wire_file_blocks_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, stream, d_digests,
+                     n, bs, last, d_out);
+  return hip_err(hipGetLastError());
+}
 
 // The end offset of every message of the run (inclusive scan of the
 // lengths), in stream-ordered scratch the caller frees with stream_free on
@@ -137,6 +190,22 @@ int wire_build(const uint8_t* d_digests, const uint32_t* d_sizes, const uint64_t
 }  // namespace sfi
 
 extern "C" {
+
+int sf_wire_file_blocks_device(const void* d_digests, uint64_t n_blocks, uint32_t block_size, uint64_t file_len,
+                               void* d_out, uint64_t cap, uint64_t* n_out, void* stream) {
+  using sfi::ceil_div;
+  if (block_size == 0 || block_size > SF_MAX_BLOCK_SIZE) return SF_EINVAL;
+  const uint64_t nb = file_len ? ceil_div(file_len, block_size) : 0;
+  if (nb != n_blocks) return SF_EINVAL;
+  const uint32_t last = nb ? (uint32_t)(file_len - (nb - 1) * block_size) : 0;
+  const uint64_t bytes = nb ? (nb - 1) * (33 + (uint64_t)digits10(block_size)) + (33 + digits10(last)) : 0;
+  if (n_out) *n_out = bytes;
+  if (bytes > cap) return SF_ENOSPC;
+  if (!nb) return SF_OK;
+  if (!d_digests || !d_out) return SF_EINVAL;
+  return sfi::launch_wire(static_cast<const uint8_t*>(d_digests), nb, block_size, last, static_cast<uint8_t*>(d_out),
+                          sfi::as_stream(stream));
+}
 
 int sf_wire_blocks_device(const void* d_digests, const uint32_t* d_sizes, uint64_t n_blocks, void* d_out,
                           uint64_t cap, uint64_t* n_out, void* stream) {

@@ -1,7 +1,7 @@
 // sha1_device.hpp -- SHA-1 building blocks for gfx950 (one lane = one message).
 //
 // The arithmetic is FIPS 180-4 SHA-1, the function the reference applies per
-// block through the `sha1 0.6.0` crate (/root/reference/src/index.rs:628-644)
+// block through the `sha1 0.6.0` crate (its src/index.rs:628-644)
 // and over the digest list in compute_blocks_hash (src/index.rs:661-682).
 //
 // Cost model (CDNA4): one 64-byte compression = 80 rounds x 5 VALU
@@ -79,17 +79,6 @@ struct Sha1 {
       e = d; d = c; c = rotl(b, 30); b = a; a = tmp;
     }
     h0 += a; h1 += b; h2 += c; h3 += d; h4 += e;
-  }
-  // Same bytes, stored write-through (sc1: global_store_dword ... sc1) so a
-  // consumer on another XCD can read them after a drain + flag, without an
-  // agent-scope release fence on this side.
-  __device__ __forceinline__ void store_writethrough(uint8_t* out20) const {
-    uint32_t* o = reinterpret_cast<uint32_t*>(out20);
-    __hip_atomic_store(o + 0, bswap32(h0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(o + 1, bswap32(h1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(o + 2, bswap32(h2), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(o + 3, bswap32(h3), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(o + 4, bswap32(h4), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
   // Digest bytes in sha1.digest().bytes() order (big-endian), as 5 words
   // ready for a little-endian store.

@@ -5,13 +5,13 @@ wave of 64 blocks; a test that means to run one of them asks here first and
 asserts the answer, so a case that no longer reaches its path fails instead of
 quietly checking another one.
 
-The conditions, and where they stand (syncfast_amd/csrc/sf_kernels.hpp unless
-another file is named):
+The conditions, and where they stand (syncfast_amd/csrc/sf_block_hash.hpp
+unless another file is named):
 
-explicit lists, `table_group` (kernel sha1_table_kernel<128, WEAK>)
+explicit lists, `table_group` in sf_table.hip (kernel sha1_table_kernel<128, WEAK>)
   * group g of the list is blocks 64g .. 64g + 63 of the processing order:
     list order, or the stable sort by length class, largest first
-    (`table_order` in sf_capi.hip, `length_class`; the launcher sorts from
+    (`table_order` in sf_table.hip, `length_class` in sf_sort.hip; the launcher sorts from
     `table_sort_min()` = TABLE_SORT_MIN blocks unless SF_TEST_TABLE_SORT
     says 0 / 1).  The round-1 reversal of sha1_table_kernel permutes whole
     groups, not a group's contents, and is left out here;
@@ -36,14 +36,14 @@ fixed tiling, `fixed_wave` (kernel sha1_fixed_kernel<128, 1, WEAK>)
     steps = (min_size / 64) / 2;
   * in `hash_wave<128, true, WEAK>` the uniform padding chunk
     (`compress_uniform`) ends a wave when pad.bytes == min_size == max_size
-    (bs a multiple of 64, `pad_schedule` in sf_capi.hip) and c_done == nfull,
+    (bs a multiple of 64, `pad_schedule` in sf_batch.cpp) and c_done == nfull,
     i.e. 2 * steps == bs / 64: "tile+pad"; any other lds_ok wave ends per
     lane: "tile"; without lds_ok "lane" (which then takes the padding chunk
     for a uniform bs % 64 == 0 wave on its own account; not told apart here).
 """
 import numpy as np
 
-TABLE_SORT_MIN = 65   # kTableSortMinBlocks, sf_capi.hip
+TABLE_SORT_MIN = 65   # kTableSortMinBlocks, sf_table.hip
 _SPAN_MAX = 0xF0000000
 
 

@@ -48,10 +48,10 @@ RETIRED_MACROS = ("SF_EXPERIMENT_SEQ", "SF_EXPERIMENT_NOLOAD", "SF_PIPE", "SF_SC
                   "SF_CLASS_BITS_FORCE", "SF_NO_CHAIN_HELPER", "SF_FIXED_WPE", "SF_STAGED_WPE", "SF_TABLE_SNAKE",
                   "SF_TABLE_LB", "SF_TABLE_WG", "SF_TABLE_ROUND", "SF_CHAIN_DEPTH", "SF_SORT_ROUNDS", "SF_LOAD_AUX",
                   "SF_LIST_LOAD_AUX", "SF_CHAIN_PRIO")
-# The only preprocessor conditionals the product sources may hold: the
-# translation-unit switch of the shared kernel header, the host compiler's
-# HIP platform define and the host SHA-NI path.
-ALLOWED_CONDITIONALS = ("SF_STREAM_TU", "__HIP_PLATFORM_AMD__", "__x86_64__", "SF_WIRE_CHUNK_DEFAULT")
+# The only preprocessor conditionals the product sources may hold: the host
+# compiler's HIP platform define, the host SHA-NI path and the wire chunk's
+# default.  No kernel source holds one.
+ALLOWED_CONDITIONALS = ("__HIP_PLATFORM_AMD__", "__x86_64__", "SF_WIRE_CHUNK_DEFAULT")
 
 
 def _product_sources():

@@ -115,7 +115,7 @@ def test_table_unsorted_overlapping_empty_blocks(gpu):
 def test_table_aligned_contiguous_blocks(gpu):
     # every block 16-B aligned and contiguous, with ragged sizes: aligned
     # waves whose sizes differ take the slot path (hash_wave_list), not the
-    # LDS tile, whose per-lane tails cost more (sf_kernels.hpp, table_group)
+    # LDS tile, whose per-lane tails cost more (sf_table.hip, table_group)
     rng = np.random.default_rng(12)
     sizes = (rng.integers(1, 600, 777) * 16 + rng.integers(0, 16, 777) * (rng.random(777) < 0.3)).astype(np.int64)
     offs = np.zeros_like(sizes)

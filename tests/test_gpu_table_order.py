@@ -198,7 +198,7 @@ def test_sorted_round_reversal_weak(gpu, knobs):
 
 def _class_keys(sizes, mbits=4):
     """length_class(n_chunks(size), mbits mantissa bits) clamped at
-    (16 << max(mbits, 4)) - 1 (sf_kernels.hpp, sf_capi.hip), in numpy."""
+    (16 << max(mbits, 4)) - 1 (sf_sort.hip, sf_table.hip), in numpy."""
     nch = (sizes.astype(np.int64) + 8) // 64 + 1
     e = np.floor(np.log2(nch)).astype(np.int64)
     k = np.where(nch < (1 << mbits), nch,
