@@ -386,6 +386,90 @@ int sf_receive_block_data_buffer(const void *wire /* host */, uint64_t n_bytes, 
                                  uint64_t cap, uint64_t *n_out, uint64_t *consumed, int *stop,
                                  uint64_t *need, uint64_t *n_bad);
 
+/* ------------------------------ sending a BLOCK_DATA run, from the device ---- */
+
+/* The source's answer to GET_BLOCK: for every request FsSource looks the
+ * digest up (Index::get_block), reads the block (read_block) and writes one
+ * BLOCK_DATA message (src/sync/fs.rs:199-208, src/sync/ssh/proto.rs:175-181).
+ * Here a whole run of such messages is built in HBM in one call.
+ *
+ * A run is owned by the library: its length is known only after a scan of the
+ * message lengths on the device, so the library allocates it (from its
+ * stream-ordered pool, which keeps the block for later runs on that stream)
+ * and hands out a handle.  sf_wire_run_info gives the device pointer (NULL for
+ * an empty run), the bytes and the messages; the bytes are complete once the
+ * building stream has run past the building call, and sf_wire_run_read /
+ * sf_wire_run_to_fd wait for exactly that themselves.  sf_wire_run_free
+ * releases the run stream-ordered (after the work `stream` holds, as
+ * sf_block_set_free); NULL is fine. */
+typedef struct sf_wire_run sf_wire_run;
+
+/* Message i = "BLOCK_DATA\n" + the 20 bytes at d_digests + 20 * i + "\n" +
+ * decimal d_sizes[i] + "\n" + src[d_src_offsets[i], + d_sizes[i]) + "\n",
+ * 34 + digits + size bytes, back to back in list order: byte for byte what
+ * write_message gives.  The reference cuts the file again in read_block to
+ * find the block's end; here the size the index holds is taken as given.
+ * Sizes are any uint32 (0: a 35-byte message), offsets any uint64, nothing is
+ * aligned beyond the lists' element types and the digest table (4 B, as
+ * everywhere); sources may overlap or repeat.  A job whose source does not lie
+ * in [0, src_len) (offset + size past 2^64 included) gives SF_ERANGE: *out =
+ * NULL, nothing is built and no byte outside the buffer is loaded.
+ * One lane per job writes the lengths, a uint64 scan turns them into end
+ * offsets, the total and the range flag come back in one 16-byte copy (the
+ * call blocks there, once), one lane per message writes its header and end
+ * byte with byte stores, and the payloads go through the block copy kernel of
+ * sf_copy_blocks_device (sf_send.hip).  Scratch: 24 n_blocks
+ * bytes plus the scan's and the copy's.  n_blocks == 0 gives an empty run,
+ * launches nothing and needs no device.  SF_EINVAL, before any device call,
+ * for a NULL out, for n_blocks > 2^32 and for a NULL or misaligned list or a
+ * NULL buffer with n_blocks > 0. */
+int sf_wire_block_data_device(const void *d_src, uint64_t src_len, const void *d_digests,
+                              const uint64_t *d_src_offsets, const uint32_t *d_sizes,
+                              uint64_t n_blocks, sf_wire_run **out, void *stream);
+
+/* A received run of GET_BLOCK requests answered in one call.  d_requests[0,
+ * n_bytes) is parsed as the reference parser reads it: message k is the 31
+ * bytes at 31 k, "GET_BLOCK\n" + 20 digest bytes of any value + "\n";
+ * *n_requests = the leading messages, *consumed = 31 * *n_requests, *stop =
+ * SF_WIRE_* for what stands at d_requests + *consumed (every proper prefix of
+ * a request is SF_WIRE_INCOMPLETE, COMPLETE and the other seven commands
+ * SF_WIRE_OTHER, a wrong byte after the digest SF_WIRE_MALFORMED).  Each
+ * digest is looked up in `set` (sf_block_set_lookup: the first present row
+ * holding it, Index::get_block) and request k becomes message k of *out with
+ * the bytes src[d_row_offsets[row], + d_row_sizes[row]) -- two device arrays
+ * with one entry per row of the set.  A repeated request is answered each
+ * time.  Requests [0, *n_answered) are answered: up to the first whose digest
+ * the set does not hold, where the reference, having answered the earlier
+ * ones, fails with "Requested block is unknown" -- the caller raises that when
+ * *n_answered < *n_requests.  A row whose block leaves [0, src_len) gives
+ * SF_ERANGE as above.  One lane per 31-byte slot tests the tag line and the
+ * end byte; the stop is decided on the host from at most 128 bytes copied
+ * back.  n_bytes == 0 gives an empty run and SF_WIRE_END; n_bytes <= 2^38.
+ * SF_EINVAL for a NULL result pointer and for a NULL set or run with
+ * n_bytes > 0.  Blocking. */
+int sf_serve_get_blocks_device(const sf_block_set *set, const uint64_t *d_row_offsets,
+                               const uint32_t *d_row_sizes, const void *d_src, uint64_t src_len,
+                               const void *d_requests, uint64_t n_bytes, sf_wire_run **out,
+                               uint64_t *n_requests, uint64_t *n_answered, uint64_t *consumed,
+                               int *stop, void *stream);
+
+/* The run's device pointer and counts (each result pointer may be NULL).
+ * SF_EINVAL for a NULL run. */
+int sf_wire_run_info(const sf_wire_run *run, const void **bytes, uint64_t *n_bytes, uint64_t *n_messages);
+
+/* Bytes [offset, offset + len) of the run to host memory.  SF_ERANGE when
+ * they do not lie in the run.  Blocking. */
+int sf_wire_run_read(const sf_wire_run *run, uint64_t offset, void *out /* host */, uint64_t len);
+
+/* The run written to fd with write(), in order, so a pipe works: the source's
+ * SSH pipe (src/sync/ssh/mod.rs).  The bytes come back in stages (64 MiB) by
+ * DMA into pinned buffers; stage k is copied while stage k - 2 is written.
+ * *n_written (may be NULL) = the bytes known written.  SF_EIO on a failed
+ * write (a closed pipe: with SIGPIPE ignored or handled, EPIPE).  Blocking. */
+int sf_wire_run_to_fd(const sf_wire_run *run, int fd, uint64_t *n_written);
+
+int sf_wire_run_free(sf_wire_run *run, void *stream);
+
 /* --------------------------- assembling the incoming files, on the device ---- */
 
 /* What the two sink states exist for: every block the destination already

@@ -119,6 +119,12 @@ def _table():
         "sf_receive_blocks_buffer": (i32, [vp, vp, u64, u64, sig, vp, u64, pu64, pu64, pint, pu64]),
         "sf_receive_block_data_device": (i32, [vp, u64, vp, vp, vp, vp, u64, pu64, pu64, pint, pu64, pu64, vp]),
         "sf_receive_block_data_buffer": (i32, [vp, u64, sig, vp, u64, pu64, pu64, pint, pu64, pu64]),
+        "sf_wire_block_data_device": (i32, [vp, u64, vp, vp, vp, u64, P(vp), vp]),
+        "sf_serve_get_blocks_device": (i32, [vp, vp, vp, vp, u64, vp, u64, P(vp), pu64, pu64, pu64, pint, vp]),
+        "sf_wire_run_info": (i32, [vp, P(vp), pu64, pu64]),
+        "sf_wire_run_read": (i32, [vp, u64, vp, u64]),
+        "sf_wire_run_to_fd": (i32, [vp, i32, pu64]),
+        "sf_wire_run_free": (i32, [vp, vp]),
         "sf_copy_blocks_device": (i32, [vp, u64, vp, u64, vp, vp, vp, vp, u64, vp, vp]),
         "sf_write_device_fd": (i32, [vp, u64, i32, u64, pu64, vp]),
         "sf_fill_splitmix_device": (i32, [vp, u64, u64, u64, vp]),

@@ -194,9 +194,11 @@ int device_state(int* dev, int* cus, DevStats** stats) {
   return SF_OK;
 }
 
-int copy_blocks(const uint8_t* d_src, uint64_t src_len, uint8_t* d_dst, uint64_t dst_len, const uint64_t* d_src_off,
-                const uint64_t* d_dst_off, const uint32_t* d_sizes, const uint8_t* d_take, uint64_t n, int* d_status,
-                hipStream_t s) {
+}  // namespace
+
+int sfi::copy_blocks(const uint8_t* d_src, uint64_t src_len, uint8_t* d_dst, uint64_t dst_len,
+                     const uint64_t* d_src_off, const uint64_t* d_dst_off, const uint32_t* d_sizes,
+                     const uint8_t* d_take, uint64_t n, int* d_status, hipStream_t s) {
   g_copy_launches.store(0, std::memory_order_relaxed);
   g_copy_dev.store(-1, std::memory_order_relaxed);
   if (n == 0) return SF_OK;
@@ -239,8 +241,6 @@ int copy_blocks(const uint8_t* d_src, uint64_t src_len, uint8_t* d_dst, uint64_t
   g_copy_dev.store(dev, std::memory_order_relaxed);
   return SF_OK;
 }
-
-}  // namespace
 
 extern "C" {
 

@@ -547,6 +547,48 @@ static int sf_write_device_fd_body(const void* d_data, uint64_t len, int fd, uin
   return rc;
 }
 
+// A built BLOCK_DATA run (sf_send.hip) written to fd with write(), in order: a
+// pipe works.  Stage k comes back by DMA into its pinned buffer, behind the
+// run's last kernel, while stage k-2 is written.  Stages are 64 MiB
+// (SF_TEST_STREAM_STAGE_MIB: a test's small ones).
+static int sf_wire_run_to_fd_body(const sf_wire_run* run, int fd, uint64_t* n_written) {
+  if (n_written) *n_written = 0;
+  if (!run || fd < 0) return SF_EINVAL;
+  if (run->n_bytes == 0) return SF_OK;
+  int cur = 0;
+  SF_HIP(hipGetDevice(&cur));
+  struct Device {
+    int back;
+    ~Device() { if (back >= 0) (void)hipSetDevice(back); }
+  } restore{cur != run->device ? cur : -1};
+  if (cur != run->device) SF_HIP(hipSetDevice(run->device));
+  const int64_t sm = knob(K_TEST_STREAM_STAGE_MIB);
+  const uint64_t len = run->n_bytes;
+  const uint64_t stage = std::min<uint64_t>(len, sm > 0 ? (uint64_t)sm << 20 : (64ull << 20));
+  const uint64_t nstages = ceil_div(len, stage);
+  HostLease res;
+  hipStream_t* st;
+  hipEvent_t* ev;
+  StageBufs sb[2];
+  int rc = res.streams(st, ev);
+  for (int i = 0; i < 2 && rc == SF_OK; i++) rc = res.pin(kSlotData + i, stage, &sb[i].pin);
+  if (rc != SF_OK) return rc;
+  for (int i = 0; i < 2; i++) SF_HIP(hipStreamWaitEvent(st[i], run->done, 0));
+  WireOut w{fd, ev, sb};
+  rc = two_stage(
+      nstages,
+      [&](uint64_t k, int b) {
+        const uint64_t o = k * stage;
+        sb[b].ddata = run->bytes + o;
+        w.bytes_of[b] = std::min(stage, len - o);
+        return w.copy_back(b, st[b]);
+      },
+      [&](uint64_t, int b) { return w.flush(b); });
+  for (int i = 0; i < 2; i++) (void)hipStreamSynchronize(st[i]);
+  if (n_written) *n_written = w.written;
+  return rc;
+}
+
 }  // extern "C"
 
 namespace {
@@ -1115,6 +1157,10 @@ int sf_wire_file_blocks_fd(const void* d_digests, uint64_t n_blocks, uint32_t bl
 int sf_write_device_fd(const void* d_data, uint64_t len, int fd, uint64_t file_offset, uint64_t* n_written,
                        void* stream) {
   return guarded([&] { return sf_write_device_fd_body(d_data, len, fd, file_offset, n_written, stream); });
+}
+
+int sf_wire_run_to_fd(const sf_wire_run* run, int fd, uint64_t* n_written) {
+  return guarded([&] { return sf_wire_run_to_fd_body(run, fd, n_written); });
 }
 
 int sf_index_buffer(const uint8_t* data, uint64_t len, uint32_t block_size, sf_block_sig* out, uint64_t cap,

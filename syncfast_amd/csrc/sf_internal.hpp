@@ -33,6 +33,9 @@
 //                 what the two parsers share is sf_recv_scan.hpp).
 //   sf_copy.hip   the block copy kernel that assembles the incoming files in
 //                 HBM (its own kernels; the arithmetic is sf_copy_plan.hpp).
+//   sf_send.hip   BLOCK_DATA runs built on the device, and a GET_BLOCK run
+//                 answered in one call (its own kernels; the rules are
+//                 sf_wire_data.hpp; the payloads go through sf_copy.hip).
 // The .cpp files use only the HIP runtime API (no kernels), so they build
 // with the host compiler.
 #pragma once
@@ -65,6 +68,18 @@
     hipError_t _e = (call);                \
     if (_e != hipSuccess) return sfi::hip_err(_e); \
   } while (0)
+
+// The opaque handle of include/syncfast_amd.h: a BLOCK_DATA run built in HBM
+// (sf_send.hip builds and frees it, sf_host.cpp streams it to a descriptor).
+// bytes: stream-ordered scratch of `device` (NULL for an empty run, which
+// needs no device); done: recorded on the building stream behind the last
+// kernel that writes the run (NULL for an empty run).
+struct sf_wire_run {
+  uint8_t* bytes;
+  uint64_t n_bytes, n_messages;
+  int device;
+  hipEvent_t done;
+};
 
 namespace sfi __attribute__((visibility("hidden"))) {
 
@@ -167,6 +182,12 @@ int wire_plan(const uint32_t* d_sizes, uint64_t n, uint64_t** d_ends, hipStream_
 int wire_chunk_ends(const uint64_t* d_ends, uint64_t n, uint64_t per, uint64_t* d_chunk_ends, hipStream_t s);
 int wire_build(const uint8_t* d_digests, const uint32_t* d_sizes, const uint64_t* d_ends, uint64_t first,
                uint64_t cnt, uint64_t base, uint8_t* d_out, hipStream_t s);
+
+// The block copy (sf_copy.hip): what sf_copy_blocks_device does, for the
+// library's own callers (sf_send.hip writes a run's payloads with it).
+int copy_blocks(const uint8_t* d_src, uint64_t src_len, uint8_t* d_dst, uint64_t dst_len, const uint64_t* d_src_off,
+                const uint64_t* d_dst_off, const uint32_t* d_sizes, const uint8_t* d_take, uint64_t n, int* d_status,
+                hipStream_t s);
 
 // Per-device resources of the host-memory entry points (streams, events,
 // device stage buffers, digest table, pinned stages), kept between calls:

@@ -4,7 +4,9 @@
 // sf_wire_parse.hpp's for FILE_BLOCK runs and built on its pieces: one
 // message at a known start (data_message), what stops a run (classify_data),
 // the serial parse of a whole run (parse_data_run) and the exact chain over a
-// list of candidate starts (walk_candidates).
+// list of candidate starts (walk_candidates).  Below them the sending side's
+// rules: the length and the header writer of a BLOCK_DATA message (written by
+// :175-181) and the serial definition of a run of GET_BLOCK requests.
 //
 // A message is "BLOCK_DATA\n" + 20 digest bytes + "\n" + a length field of 1
 // to 15 bytes + "\n" (the header, H = 34 to 48 bytes) + `length` payload bytes
@@ -121,6 +123,76 @@ inline uint64_t walk_candidates(const uint64_t* pos, const uint64_t* len, uint64
     if (j == count || pos[j] != next) return k;
     i = j;
   }
+}
+
+// ---- the sending side: BLOCK_DATA messages written, GET_BLOCK runs read ----
+// (sf_send.hip's kernels call the constexpr functions; tests/native/
+// block_data_write.cpp runs all of them on a CPU)
+
+constexpr uint32_t digits10(uint32_t v) {
+  uint32_t d = 1;
+  while (v >= 10) { v /= 10; ++d; }
+  return d;
+}
+
+// Header and whole message of a payload of `size` bytes as write_message
+// writes them (proto.rs:175-181): 11 for the tag, 20 for the digest, 1, the
+// decimal size, 1; then the payload and 1.
+constexpr uint32_t block_data_header_len(uint32_t size) { return kSizeAt + digits10(size) + 1; }
+constexpr uint64_t block_data_len(uint32_t size) { return (uint64_t)block_data_header_len(size) + size + 1; }
+
+// Everything of a message but its payload, byte stores only: the header at
+// `head` ("BLOCK_DATA\n" + digest[0, 20) + "\n" + size in decimal + "\n") and
+// the "\n" that ends the message at `end` (= head + header + size for a
+// message in one piece).  Returns the header's length; no byte between
+// head + that and `end` is touched.
+constexpr uint32_t write_block_data(uint8_t* head, uint8_t* end, const uint8_t* digest, uint32_t size) {
+  const char tag[kTag] = {'B', 'L', 'O', 'C', 'K', '_', 'D', 'A', 'T', 'A', '\n'};
+  for (uint32_t k = 0; k < kTag; k++) head[k] = (uint8_t)tag[k];
+  for (uint32_t k = 0; k < kDigest; k++) head[kTag + k] = digest[k];
+  head[kTag + kDigest] = '\n';
+  const uint32_t nd = digits10(size);
+  uint32_t v = size;
+  for (uint32_t k = nd; k-- > 0;) { head[kSizeAt + k] = (uint8_t)('0' + v % 10); v /= 10; }
+  head[kSizeAt + nd] = '\n';
+  *end = '\n';
+  return kSizeAt + nd + 1;
+}
+
+// A GET_BLOCK message (proto.rs:170-174): "GET_BLOCK\n" + 20 digest bytes of
+// any value + "\n", 31 bytes, so message k of a run stands at 31 k.
+constexpr uint32_t kGetTag = 10, kGetBlock = kGetTag + kDigest + 1;
+
+// The test one lane makes of one 31-byte slot: the tag line and the end byte.
+constexpr bool is_get_block(const uint8_t* b) {
+  return (b[0] == 'G') & (b[1] == 'E') & (b[2] == 'T') & (b[3] == '_') & (b[4] == 'B') & (b[5] == 'L') &
+         (b[6] == 'O') & (b[7] == 'C') & (b[8] == 'K') & (b[9] == '\n') & (b[kGetTag + kDigest] == '\n');
+}
+
+// What stands at b (avail bytes to the end of the buffer, of which the first
+// min(avail, 31) are read) in a run of GET_BLOCK messages: kHeader for a whole
+// message, else why the run stops here.
+inline int classify_get_block(const uint8_t* b, uint64_t avail) {
+  if (avail == 0) return kEnd;
+  bool raise = false;
+  const int c = line_end(b, avail, kCommandMax, &raise);
+  if (c < 0) return raise ? kMalformed : kIncomplete;  // "Unterminated command"
+  if (c != (int)kGetTag - 1 || memcmp(b, "GET_BLOCK", kGetTag - 1) != 0)
+    return is_command(b, (size_t)c) ? kOther : kMalformed;  // "Unknown command"
+  if (avail < kGetBlock) return kIncomplete;
+  return b[kGetTag + kDigest] == '\n' ? kHeader : kMalformed;  // "Unterminated digest"
+}
+
+// The run at b[0, n) as the reference parser reads it: *count = the leading
+// GetBlock messages (their digests at b + 31 k + 10), *consumed = 31 * count,
+// *stop = what stands after them.
+inline void parse_get_block_run(const uint8_t* b, uint64_t n, uint64_t* count, uint64_t* consumed, int* stop) {
+  uint64_t k = 0;
+  int c;
+  while ((c = classify_get_block(b + kGetBlock * k, n - kGetBlock * k)) == kHeader) k++;
+  *count = k;
+  *consumed = kGetBlock * k;
+  *stop = c;
 }
 
 }  // namespace sfwp

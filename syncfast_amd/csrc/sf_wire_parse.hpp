@@ -80,6 +80,15 @@ inline int line_end(const uint8_t* b, uint64_t avail, uint32_t limit, bool* rais
   return -1;
 }
 
+// Whether the c bytes at b are one of the parser's nine command names.
+inline bool is_command(const uint8_t* b, size_t c) {
+  static const char* const commands[9] = {"FILE_ENTRY", "END_FILES",  "GET_FILE",   "FILE_START", "FILE_END",
+                                          "GET_BLOCK",  "FILE_BLOCK", "BLOCK_DATA", "COMPLETE"};
+  for (const char* o : commands)
+    if (strlen(o) == c && memcmp(b, o, c) == 0) return true;
+  return false;
+}
+
 // The header at b, read from its first min(avail, 48) bytes alone (avail: the
 // bytes to the end of the buffer), for a run of `tag` messages ("FILE_BLOCK"
 // or "BLOCK_DATA": ten bytes, digest and size field laid out alike): kHeader
@@ -93,11 +102,7 @@ inline int header(const uint8_t* b, uint64_t avail, const char* tag, uint32_t* l
   const int c = line_end(b, avail, kCommandMax, &raise);
   if (c < 0) return raise ? kMalformed : kIncomplete;  // "Unterminated command"
   if (c != (int)kTag - 1 || memcmp(b, tag, kTag - 1) != 0) {
-    static const char* const commands[9] = {"FILE_ENTRY", "END_FILES",  "GET_FILE",   "FILE_START", "FILE_END",
-                                            "GET_BLOCK",  "FILE_BLOCK", "BLOCK_DATA", "COMPLETE"};
-    for (const char* o : commands)
-      if (strlen(o) == (size_t)c && memcmp(b, o, (size_t)c) == 0) return kOther;
-    return kMalformed;  // "Unknown command"
+    return is_command(b, (size_t)c) ? kOther : kMalformed;  // "Unknown command"
   }
   if (avail < kTag + kDigest + 1) return kIncomplete;
   if (b[kTag + kDigest] != '\n') return kMalformed;  // "Unterminated digest"

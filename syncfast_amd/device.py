@@ -480,6 +480,49 @@ class BlockSet:
         return (digests[:k], sizes[:k].view(torch.uint32), offsets[:k], rows[:k], consumed.value, stop.value,
                 end.value)
 
+    def serve(self, requests: torch.Tensor, src: torch.Tensor, row_offsets: torch.Tensor, row_sizes: torch.Tensor):
+        """The source's answer to a received run of GET_BLOCK requests, in one
+        call (sf_serve_get_blocks_device): ``requests`` (a flat uint8 HBM
+        tensor) is parsed as ``wire.Parser`` reads it, every digest is looked
+        up in this set, and request k becomes the BLOCK_DATA message carrying
+        ``src[row_offsets[row] : + row_sizes[row]]`` -- ``row_offsets`` int64
+        and ``row_sizes`` int32/uint32, one entry per row of the set, on its
+        device like ``src``.  Returns (run, n_requests, n_answered, consumed,
+        stop): ``run`` a ``wire.BlockDataRun`` of the first ``n_answered``
+        answers, which stop at the first request whose digest the set does not
+        hold (the reference answers those before it and then fails with
+        "Requested block is unknown": raise that when ``n_answered <
+        n_requests``); ``consumed`` = 31 * ``n_requests`` and ``stop`` the
+        SF_WIRE_* class of what stands at ``requests[consumed:]``.  Blocking."""
+        from .wire import BlockDataRun
+        dev = self.table.device
+        _require_device(requests, "requests", torch.uint8, dev)
+        _require_device(src, "src", torch.uint8, dev)
+        _require_device(row_offsets, "row_offsets", torch.int64, dev)
+        if requests.dim() != 1:
+            raise ValueError("requests must be a flat uint8 tensor")
+        n = self.table.shape[0]
+        if (not isinstance(row_sizes, torch.Tensor) or row_sizes.dtype not in (torch.int32, torch.uint32)
+                or row_sizes.device != dev or row_sizes.numel() != n or row_offsets.numel() != n):
+            raise ValueError("row_offsets (int64) and row_sizes (32-bit) must hold one entry per row of the set")
+        if not self._h:
+            raise ValueError("BlockSet is closed")
+        h, stop = ctypes.c_void_p(), ctypes.c_int(0)
+        nreq, nans, consumed = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+        with _on(dev, self.stream):
+            row_sizes = row_sizes.contiguous()
+            # the library wants its buffers even where nothing can be read from them
+            buf = src if src.numel() else torch.empty(1, dtype=torch.uint8, device=dev)
+            if n == 0:
+                row_offsets, row_sizes = torch.zeros(1, dtype=torch.int64, device=dev), torch.zeros(
+                    1, dtype=torch.int32, device=dev)
+            check(lib().sf_serve_get_blocks_device(self._h, _ptr(row_offsets), _ptr(row_sizes), buf.data_ptr(),
+                                                   src.numel(), _ptr(requests), requests.numel(), ctypes.byref(h),
+                                                   ctypes.byref(nreq), ctypes.byref(nans), ctypes.byref(consumed),
+                                                   ctypes.byref(stop), _stream_ptr(self.table, self.stream)),
+                  "sf_serve_get_blocks_device")
+        return BlockDataRun(h, dev, self.stream), nreq.value, nans.value, consumed.value, stop.value
+
     def close(self) -> None:
         if self._h:
             with _on(self.table.device, self.stream):

@@ -7,7 +7,11 @@ GET_BLOCK, BLOCK_DATA and COMPLETE.  ``file_blocks_device`` produces a whole
 file's FILE_BLOCK run on the GPU straight from the HBM digest table
 (C-ABI sf_wire_file_blocks_device), as FsSource streams it after FILE_START
 (src/sync/fs.rs:217-233).  ``Parser`` is the receiving side (proto.rs:189-477):
-the incremental framing parser a destination runs over the same bytes."""
+the incremental framing parser a destination runs over the same bytes.
+``block_data_device`` builds the source's BLOCK_DATA run on the GPU
+(sf_wire_block_data_device) as a ``BlockDataRun``, which
+``device.BlockSet.serve`` also returns for a received run of GET_BLOCK
+requests."""
 from __future__ import annotations
 
 import ctypes
@@ -279,6 +283,121 @@ def block_data_stats():
     out = (ctypes.c_uint64 * 4)()
     check(lib().sf_test_block_data_stats(out), "sf_test_block_data_stats")
     return tuple(int(v) for v in out)
+
+
+class BlockDataRun:
+    """A run of BLOCK_DATA messages built in HBM and owned by the library
+    (sf_wire_run): what ``block_data_device`` and ``device.BlockSet.serve``
+    return.  ``nbytes`` / ``n_messages`` / ``data_ptr`` describe it; the bytes
+    are complete once the building stream has run past the build, and every
+    method here waits for that or runs on that stream.  ``close()`` (also on
+    leaving a ``with`` block, and when the object is dropped) gives the memory
+    back, stream-ordered."""
+
+    def __init__(self, handle, device, stream=None):
+        self._h, self.device, self.stream = handle, device, stream
+        p, nb, nm = ctypes.c_void_p(), ctypes.c_uint64(0), ctypes.c_uint64(0)
+        check(lib().sf_wire_run_info(self._h, ctypes.byref(p), ctypes.byref(nb), ctypes.byref(nm)), "sf_wire_run_info")
+        self.data_ptr, self.nbytes, self.n_messages = p.value or 0, nb.value, nm.value
+
+    def _open(self):
+        if not self._h:
+            raise ValueError("BlockDataRun is closed")
+
+    def bytes(self, offset: int = 0, length: int = None) -> bytes:
+        """``length`` bytes of the run from ``offset`` (default: all), copied
+        to the host (sf_wire_run_read)."""
+        self._open()
+        length = self.nbytes - offset if length is None else length
+        buf = ctypes.create_string_buffer(max(length, 1))
+        check(lib().sf_wire_run_read(self._h, offset, buf, length), "sf_wire_run_read")
+        return buf.raw[:length]
+
+    @property
+    def __cuda_array_interface__(self):
+        return {"shape": (self.nbytes,), "typestr": "|u1", "data": (self.data_ptr, False), "version": 2,
+                "strides": None}
+
+    def tensor(self):
+        """The run as a uint8 HBM tensor: a view of the library's memory
+        through ``__cuda_array_interface__``, valid until ``close()`` (the
+        tensor keeps this object alive)."""
+        import torch
+        self._open()
+        if self.nbytes == 0:
+            return torch.empty(0, dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            return torch.as_tensor(self, device=self.device)
+
+    def receive(self, verify: bool = True):
+        """The run handed straight to ``receive_block_data_device``, on the
+        stream it was built on."""
+        return receive_block_data_device(self.tensor(), verify=verify, stream=self.stream)
+
+    def to_fd(self, fd: int) -> int:
+        """The run written to ``fd`` with write() through the pinned stages
+        (sf_wire_run_to_fd); a pipe works.  Returns the bytes written; a failed
+        write raises SfError(SF_EIO) whose ``written`` attribute holds the
+        bytes known written."""
+        self._open()
+        nw = ctypes.c_uint64(0)
+        rc = lib().sf_wire_run_to_fd(self._h, int(fd), ctypes.byref(nw))
+        if rc != SF_OK:
+            from ._lib import SfError
+            err = SfError(rc, "sf_wire_run_to_fd")
+            err.written = nw.value
+            raise err
+        return nw.value
+
+    def close(self) -> None:
+        if self._h:
+            h, self._h = self._h, None
+            if self.data_ptr:
+                from . import device
+                import torch
+                with device._on(self.device, self.stream):
+                    check(lib().sf_wire_run_free(h, torch.cuda.current_stream(self.device).cuda_stream),
+                          "sf_wire_run_free")
+            else:
+                check(lib().sf_wire_run_free(h, None), "sf_wire_run_free")
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def block_data_device(src, digests, src_offsets, sizes, stream=None) -> BlockDataRun:
+    """The BLOCK_DATA run of an explicit job list, built on the device
+    (sf_wire_block_data_device): message i carries ``src[src_offsets[i] : +
+    sizes[i]]`` under ``digests[i]``, byte for byte what ``write_message``
+    gives.  ``src`` uint8, ``digests`` uint8[n, 20], ``src_offsets`` int64[n]
+    and ``sizes`` int32/uint32[n] (bit pattern taken as uint32) are HBM
+    tensors on one device.  A job outside ``src`` raises SfError(SF_ERANGE)
+    and nothing is built.  Blocking, for one read-back."""
+    torch, dev = _device(src, "src")
+    dev._require_device(digests, "digests", torch.uint8, src.device)
+    dev._require_device(src_offsets, "src_offsets", torch.int64, src.device)
+    n = digests.shape[0]
+    _check_sizes(torch, sizes, digests)
+    if src_offsets.numel() != n:
+        raise ValueError("src_offsets and sizes differ in length")
+    h = ctypes.c_void_p()
+    with dev._on(src.device, stream):
+        sizes = sizes.contiguous()
+        # the library wants a buffer even when every size is 0
+        buf = src if src.numel() else torch.empty(1, dtype=torch.uint8, device=src.device)
+        check(lib().sf_wire_block_data_device(buf.data_ptr(), src.numel(), dev._ptr(digests, n),
+                                              dev._ptr(src_offsets, n), dev._ptr(sizes, n), n, ctypes.byref(h),
+                                              _stream(torch, src)), "sf_wire_block_data_device")
+    return BlockDataRun(h, src.device, stream)
 
 
 def blocks_to_fd(digests, sizes, fd: int, stream=None) -> int:
