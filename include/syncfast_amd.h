@@ -470,6 +470,96 @@ int sf_wire_run_to_fd(const sf_wire_run *run, int fd, uint64_t *n_written);
 
 int sf_wire_run_free(sf_wire_run *run, void *stream);
 
+/* ----------------------- the destination's missing blocks, on the device ---- */
+
+/* The two steps between the runs.  After the FILE_BLOCK runs the sink lists
+ * its rows with present = 0 and sends one GET_BLOCK per row
+ * (Index::list_missing_blocks and src/sync/fs.rs:485-493, written by
+ * src/sync/ssh/proto.rs:170-174); for every BLOCK_DATA that comes back it
+ * asks the index where that hash is wanted (list_block_locations), writes the
+ * payload at each such row and marks it present, one query and one update per
+ * message (fs.rs:505-510).  Here the list of missing rows stays in HBM: its
+ * request run is built there, and a parsed BLOCK_DATA run is joined against
+ * it there, straight into the lists sf_copy_blocks_device takes
+ * (sf_want.hip). */
+
+/* The request run of a table of n_rows rows, d_digests + 20 * i the digest of
+ * row i (4-B aligned, rowid order).  Row i asks when d_rows is NULL or
+ * d_rows[i] < 0 -- d_rows is the array sf_receive_blocks_device wrote (8-B
+ * aligned) -- and d_take is NULL or d_take[i] != 0 (bytes, any address; for
+ * instance the negation of a present array).  Message k of *out is the 31
+ * bytes "GET_BLOCK\n" + digest + "\n" of the k-th asking row, in row order:
+ * with distinct == 0 byte for byte write_message over list_missing_blocks,
+ * whose SELECT has no DISTINCT -- a digest missing in three rows is requested
+ * three times, and answered three times.  With distinct != 0 only the first
+ * asking row of each digest asks (a block set over the asking rows, a lookup
+ * of every row's own digest: a row asks when the answer is itself).  A digest
+ * is 20 bytes of any value.
+ * *out is the run handle above (sf_wire_run_info, _read, _to_fd, _free);
+ * *n_requests (may be NULL) = its messages.  One lane per row writes a flag,
+ * a uint64 scan numbers the asking rows, the count comes back (the call
+ * blocks there, once), the run is allocated from the stream-ordered pool and
+ * one lane per row writes its message with byte stores.  Scratch: 9 n_rows
+ * bytes (17 with distinct, plus the set's 16 to 32) plus the scan's.
+ * n_rows == 0 gives an empty run, launches nothing and needs no device; no
+ * row asking gives an empty run too.  SF_EINVAL, before any device call, for
+ * a NULL out, for n_rows > 2^31, for a NULL or 4-B misaligned d_digests with
+ * n_rows > 0 and for a d_rows that is not 8-B aligned. */
+int sf_wire_get_blocks_device(const void *d_digests /* n_rows x 20 B: 4-B aligned */,
+                              const int64_t *d_rows /* may be NULL */, const uint8_t *d_take /* may be NULL */,
+                              uint64_t n_rows, int distinct, sf_wire_run **out, uint64_t *n_requests,
+                              void *stream);
+
+/* The sink's GetBlocks state (fs.rs:503-516) for a whole parsed run, as one
+ * join.  Rows: the destination's incomplete rows in rowid order --
+ * d_row_digests (20 B each, 4-B aligned), d_row_sizes, d_row_dst[r] = where
+ * row r's block lies in the image allocation (its file's base plus its
+ * offset; 8-B aligned), d_row_present[r] (bytes; 0 = the row still waits).
+ * Messages: exactly the outputs of sf_receive_block_data_device, d_msg_ok its
+ * d_ok (NULL: all ok, an unverified run).
+ *
+ * For a waiting row r, m = the lowest-numbered ok message whose digest is the
+ * row's (sf_block_set_build over the messages, a lookup of the row digests).
+ * When d_msg_sizes[m] == d_row_sizes[r] the row yields a job; jobs are
+ * numbered in row order, and job k is d_src_offsets[k] =
+ * d_msg_data_offsets[m], d_dst_offsets[k] = d_row_dst[r], d_sizes[k],
+ * d_job_rows[k] = r, d_job_msgs[k] = m; d_row_present[r] becomes 1 and
+ * d_msg_uses[m] (may be NULL; n_msgs entries, all written: 0 for a message no
+ * row wants) counts it.  When the sizes differ the row stays missing and
+ * *n_size_mismatch counts it.  That is stricter than the reference, which
+ * writes the payload whatever the row says; it is what makes the jobs'
+ * destinations disjoint whenever the rows' own ranges are -- rows tile their
+ * files -- so the first *n_jobs entries of the three lists are ONE
+ * sf_copy_blocks_device call, with no sort.  *n_left = the rows still 0
+ * afterwards (what check_temp_files asks for).
+ *
+ * For a verified run equal digests mean equal payloads, so the image is the
+ * reference's: every payload at every location, the later write winning.  In
+ * an unverified run that carries two different payloads under one digest the
+ * FIRST is taken here; the reference keeps the last.
+ *
+ * SF_ENOSPC with *n_jobs = the need when the jobs exceed cap or one of the
+ * five job lists is NULL (a query): then nothing is marked, no job and no
+ * d_msg_uses entry is written, and *n_left counts the rows that wait now.
+ * One lane per row classes it, the waiting rows and the mismatches are
+ * counted with one atomic per wave, a uint64 scan numbers the jobs, the three
+ * counts come back in one 24-byte copy (the call blocks there, once), and one
+ * lane per row writes its job.  Scratch: 17 n_rows bytes plus the set's (16
+ * to 32 per message) and the scan's.  n_rows == 0 launches nothing but the
+ * clearing of d_msg_uses; n_msgs == 0 nothing but the count for *n_left.
+ * SF_EINVAL, before any device call, for a NULL n_jobs, n_left or
+ * n_size_mismatch, for a count above 2^31, for a NULL row list with
+ * n_rows > 0 or message list with n_msgs > 0, and for a misaligned list (4 B
+ * for digests, sizes and d_msg_uses, 8 B for the 64-bit lists).  Blocking. */
+int sf_place_block_data_device(const void *d_row_digests, const uint32_t *d_row_sizes, const uint64_t *d_row_dst,
+                               uint8_t *d_row_present /* in/out */, uint64_t n_rows,
+                               const void *d_msg_digests, const uint32_t *d_msg_sizes,
+                               const uint64_t *d_msg_data_offsets, const uint8_t *d_msg_ok /* NULL: all */,
+                               uint64_t n_msgs, uint64_t *d_src_offsets, uint64_t *d_dst_offsets,
+                               uint32_t *d_sizes, int64_t *d_job_rows, int64_t *d_job_msgs, uint64_t cap,
+                               uint32_t *d_msg_uses /* may be NULL */, uint64_t *n_jobs, uint64_t *n_left,
+                               uint64_t *n_size_mismatch, void *stream);
+
 /* --------------------------- assembling the incoming files, on the device ---- */
 
 /* What the two sink states exist for: every block the destination already

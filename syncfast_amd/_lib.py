@@ -125,6 +125,9 @@ def _table():
         "sf_wire_run_read": (i32, [vp, u64, vp, u64]),
         "sf_wire_run_to_fd": (i32, [vp, i32, pu64]),
         "sf_wire_run_free": (i32, [vp, vp]),
+        "sf_wire_get_blocks_device": (i32, [vp, vp, vp, u64, i32, P(vp), pu64, vp]),
+        "sf_place_block_data_device": (i32, [vp, vp, vp, vp, u64, vp, vp, vp, vp, u64, vp, vp, vp, vp, vp, u64, vp,
+                                            pu64, pu64, pu64, vp]),
         "sf_copy_blocks_device": (i32, [vp, u64, vp, u64, vp, vp, vp, vp, u64, vp, vp]),
         "sf_write_device_fd": (i32, [vp, u64, i32, u64, pu64, vp]),
         "sf_fill_splitmix_device": (i32, [vp, u64, u64, u64, vp]),

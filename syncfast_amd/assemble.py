@@ -10,7 +10,8 @@ payload (fs.rs:505-510), then ``finish`` renames the temp files
 temp file, filled by the block copy kernel (``device.copy_blocks``,
 sf_copy_blocks_device) in one launch per list, checked as a whole against the
 rows the source announced, and written to the temp file's descriptor
-(``device.write_to_fd``).
+(``device.write_to_fd``).  A job list that is on the device already -- the join
+of ``device.place_block_data`` -- goes in as it is (``apply_jobs``).
 """
 from __future__ import annotations
 
@@ -162,6 +163,27 @@ class FileImages:
         for jobs in rounds:
             self._copy(src, jobs, stream)
         return len(rounds)
+
+    def base(self, name) -> int:
+        """Where byte 0 of temp file ``name`` lies in the allocation
+        (``buffer``): a row's ``dst`` for ``device.place_block_data`` is this
+        plus the row's offset."""
+        return self._place(name, 0, 0)
+
+    def apply_jobs(self, src: torch.Tensor, src_offsets: torch.Tensor, dst_offsets: torch.Tensor,
+                   sizes: torch.Tensor, stream: Optional[torch.cuda.Stream] = None) -> None:
+        """Carry out a job list that is on the device already -- what
+        ``device.place_block_data`` returned: ``src[src_offsets[k] : +
+        sizes[k]]`` goes to ``dst_offsets[k]`` of the allocation.  One
+        ``copy_blocks`` call and no host pass over the jobs: their
+        destinations are disjoint because the rows they come from are.  A job
+        outside ``src`` or the allocation is not copied and raises
+        SfError(SF_ERANGE) (the kernel's status word, read back after the
+        copy)."""
+        if sizes.numel() == 0:
+            return
+        self._after_fill(stream)
+        _device.copy_blocks(src, self.buffer, src_offsets, dst_offsets, sizes, check_range=True, stream=stream)
 
     def _read_local(self, from_name) -> torch.Tensor:
         key = _name_str(from_name)

@@ -36,6 +36,10 @@
 //   sf_send.hip   BLOCK_DATA runs built on the device, and a GET_BLOCK run
 //                 answered in one call (its own kernels; the rules are
 //                 sf_wire_data.hpp; the payloads go through sf_copy.hip).
+//   sf_want.hip   the destination's GET_BLOCK run built from its missing rows,
+//                 and a parsed BLOCK_DATA run joined against them into a copy
+//                 list (its own kernels; the rules are sf_want_plan.hpp; the
+//                 lookups are sf_match.hip's).
 // The .cpp files use only the HIP runtime API (no kernels), so they build
 // with the host compiler.
 #pragma once

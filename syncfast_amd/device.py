@@ -32,7 +32,7 @@ __all__ = [
     "index_device_weak", "index_device_blocks_weak", "BatchStream",
     "fill_splitmix", "splitmix_tensor", "BlockSet", "index_device_multi",
     "cut_device_zpaq", "index_device_zpaq", "zpaq_segment_len", "zpaq_device_stats",
-    "copy_blocks", "copy_stats", "write_to_fd",
+    "copy_blocks", "copy_stats", "write_to_fd", "get_block_requests", "place_block_data",
 ]
 
 
@@ -652,6 +652,120 @@ def copy_blocks(src: torch.Tensor, dst: torch.Tensor, src_offsets: torch.Tensor,
                                           _stream_ptr(src, stream)), "sf_copy_blocks_device")
         if status is not None and int(status.item()) != 0:
             raise SfError(SF_ERANGE, "sf_copy_blocks_device")
+
+
+def _flags(t: Optional[torch.Tensor], name: str, n: int, dev: torch.device) -> Optional[torch.Tensor]:
+    """A byte-flag list (uint8, or bool seen as bytes) of ``n`` entries."""
+    if t is None:
+        return None
+    if isinstance(t, torch.Tensor) and t.dtype == torch.bool:
+        t = t.view(torch.uint8)
+    _require_device(t, name, torch.uint8, dev)
+    if t.numel() != n:
+        raise ValueError(f"{name} must hold one flag per entry ({n})")
+    return t
+
+
+def _table20(t: torch.Tensor, name: str, dev: Optional[torch.device] = None) -> int:
+    _require_device(t, name, torch.uint8, dev)
+    if t.dim() != 2 or t.shape[1] != 20:
+        raise ValueError(f"{name} must be uint8[n, 20]")
+    return t.shape[0]
+
+
+def _list32(t: torch.Tensor, name: str, n: int, dev: torch.device) -> None:
+    if (not isinstance(t, torch.Tensor) or t.dtype not in (torch.int32, torch.uint32) or t.device != dev
+            or t.numel() != n or not t.is_contiguous()):
+        raise ValueError(f"{name} must be a contiguous 32-bit tensor of {n} entries on {dev}")
+
+
+def _list64(t: torch.Tensor, name: str, n: int, dev: torch.device) -> None:
+    _require_device(t, name, torch.int64, dev)
+    if t.numel() != n:
+        raise ValueError(f"{name} must hold {n} entries")
+
+
+def get_block_requests(digests: torch.Tensor, rows: Optional[torch.Tensor] = None,
+                       take: Optional[torch.Tensor] = None, distinct: bool = False,
+                       stream: Optional[torch.cuda.Stream] = None):
+    """The destination's GET_BLOCK run, built on the device
+    (sf_wire_get_blocks_device): ``digests`` uint8[n, 20] are a table's rows
+    in rowid order; row i asks when ``rows`` is None or ``rows[i] < 0`` (int64,
+    as ``BlockSet.receive`` returns them) and ``take`` is None or ``take[i]``
+    is not 0 (uint8 or bool).  Message k is ``write_message("GetBlock", ...)``
+    of the k-th asking row: over the rows with present = 0 that is byte for
+    byte the join over ``Index.list_missing_blocks()``, a digest missing in
+    three rows asked for three times (src/sync/fs.rs:485-493).  With
+    ``distinct`` only the first asking row of each digest asks.  Returns
+    (run, n_requests): ``run`` a ``wire.BlockDataRun`` (``bytes``, ``tensor``,
+    ``to_fd``, ``close``).  Blocking, for one read-back."""
+    from .wire import BlockDataRun
+    n = _table20(digests, "digests")
+    dev = digests.device
+    if rows is not None:
+        _list64(rows, "rows", n, dev)
+    take = _flags(take, "take", n, dev)
+    h, nreq = ctypes.c_void_p(), ctypes.c_uint64(0)
+    with _on(dev, stream):
+        check(lib().sf_wire_get_blocks_device(_ptr(digests, n), _ptr(rows, n), _ptr(take, n), n, int(bool(distinct)),
+                                              ctypes.byref(h), ctypes.byref(nreq), _stream_ptr(digests, stream)),
+              "sf_wire_get_blocks_device")
+    return BlockDataRun(h, dev, stream), nreq.value
+
+
+def place_block_data(row_digests: torch.Tensor, row_sizes: torch.Tensor, row_dst: torch.Tensor,
+                     row_present: torch.Tensor, msg_digests: torch.Tensor, msg_sizes: torch.Tensor,
+                     msg_offsets: torch.Tensor, msg_ok: Optional[torch.Tensor] = None,
+                     stream: Optional[torch.cuda.Stream] = None):
+    """A parsed BLOCK_DATA run joined against the destination's incomplete
+    rows, on the device (sf_place_block_data_device): the sink's per-message
+    ``list_block_locations`` + ``mark_block_present`` loop
+    (src/sync/fs.rs:505-510) as one call.
+
+    Rows, in rowid order: ``row_digests`` uint8[n, 20], ``row_sizes``
+    int32/uint32[n], ``row_dst`` int64[n] (where the row's block lies in the
+    image allocation: ``FileImages.base(name) + offset``) and ``row_present``
+    uint8/bool[n], 0 where the row still waits -- updated in place.  Messages:
+    what ``wire.receive_block_data_device`` returned (``msg_ok`` its ``ok``;
+    None: all).  A waiting row takes the lowest-numbered ok message with its
+    digest; when that payload has the row's size the row becomes a job and is
+    marked present, else it stays missing and is counted as a size mismatch.
+
+    Returns (src_offsets int64, dst_offsets int64, sizes int32, job_rows
+    int64, job_msgs int64, msg_uses int32[m], n_left, n_size_mismatch): the
+    jobs in row order -- their destinations are disjoint when the rows' are,
+    so the first three lists are one ``copy_blocks`` call -- the row and the
+    message of each job, how many jobs each message serves (0: nobody wanted
+    it), the rows still waiting and the mismatches.  Blocking."""
+    n = _table20(row_digests, "row_digests")
+    dev = row_digests.device
+    m = _table20(msg_digests, "msg_digests", dev)
+    _list32(row_sizes, "row_sizes", n, dev)
+    _list64(row_dst, "row_dst", n, dev)
+    if row_present is None:
+        raise ValueError("row_present is an output too: pass a tensor")
+    present = _flags(row_present, "row_present", n, dev)
+    _list32(msg_sizes, "msg_sizes", m, dev)
+    _list64(msg_offsets, "msg_offsets", m, dev)
+    msg_ok = _flags(msg_ok, "msg_ok", m, dev)
+    n_jobs, n_left, n_bad = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+    with _on(dev, stream):
+        uses = torch.empty(m, dtype=torch.int32, device=dev)
+
+        def call(cap):
+            a = max(cap, 1)
+            src, dst, rows, msgs = (torch.empty(a, dtype=torch.int64, device=dev) for _ in range(4))
+            sizes = torch.empty(a, dtype=torch.int32, device=dev)
+            rc = lib().sf_place_block_data_device(
+                _ptr(row_digests, n), _ptr(row_sizes, n), _ptr(row_dst, n), _ptr(present, n), n,
+                _ptr(msg_digests, m), _ptr(msg_sizes, m), _ptr(msg_offsets, m), _ptr(msg_ok, m), m,
+                src.data_ptr(), dst.data_ptr(), sizes.data_ptr(), rows.data_ptr(), msgs.data_ptr(), cap,
+                _ptr(uses, m), ctypes.byref(n_jobs), ctypes.byref(n_left), ctypes.byref(n_bad),
+                _stream_ptr(row_digests, stream))
+            return rc, n_jobs.value, (src, dst, sizes, rows, msgs)
+        # one job per message is the usual run; a digest wanted in several rows needs more
+        k, lists = retry_enospc(call, min(n, m), 2, "sf_place_block_data_device")
+    return (*(t[:k] for t in lists), uses, n_left.value, n_bad.value)
 
 
 def write_to_fd(t: torch.Tensor, fd: int, offset: int = 0, stream: Optional[torch.cuda.Stream] = None) -> int:

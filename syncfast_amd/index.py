@@ -507,6 +507,91 @@ class Index:
                                                  ok.cpu().numpy() if verify else None)
         return writes, rejected, consumed
 
+    def missing_rows(self) -> List[Tuple[int, int, Optional[PurePath], int, int, HashDigest]]:
+        """The rows ``list_missing_blocks`` reads (present = 0), in the same
+        rowid order, each with where it lies: (rowid, file_id, name, offset,
+        size, hash).  ``name`` is None for a row whose file is gone."""
+        rows = self.db.execute(
+            "SELECT blocks.rowid, blocks.file_id, files.name, blocks.offset, blocks.size, blocks.hash FROM blocks "
+            "LEFT JOIN files ON files.file_id = blocks.file_id WHERE blocks.present = 0 ORDER BY blocks.rowid;")
+        return [(int(r[0]), int(r[1]), PurePath(r[2]) if r[2] is not None else None, int(r[3]), int(r[4]),
+                 HashDigest.from_sql(r[5])) for r in rows]
+
+    @staticmethod
+    def _digest_table(rows, dev):
+        import torch
+        raw = b"".join(r[5].bytes for r in rows)
+        if not raw:
+            return torch.empty((0, 20), dtype=torch.uint8, device=dev)
+        return torch.frombuffer(bytearray(raw), dtype=torch.uint8).reshape(-1, 20).to(dev)
+
+    def get_block_requests(self, device=None, distinct: bool = False):
+        """The GET_BLOCK run the sink sends after the FILE_BLOCK runs
+        (src/sync/fs.rs:485-493), built on the device from ``missing_rows()``
+        (``device.get_block_requests``): byte for byte the join of
+        ``write_message("GetBlock", h)`` over ``list_missing_blocks()``, or
+        with ``distinct`` one request per digest.  Returns the run (a
+        ``wire.BlockDataRun``: ``bytes()``, ``to_fd(fd)``, ``close()``)."""
+        import torch
+
+        from . import device as _device
+        dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        run, _n = _device.get_block_requests(self._digest_table(self.missing_rows(), dev), distinct=distinct)
+        return run
+
+    def place_block_data(self, data, images, device=None, verify: bool = True):
+        """``receive_block_data`` and ``FileImages.apply_writes`` in one, with
+        the join between them on the device: the run is parsed and verified
+        (``wire.receive_block_data_device``), joined against
+        ``missing_rows()`` (``device.place_block_data``: every waiting row
+        takes the first verified message with its digest and its size), the
+        jobs are copied into ``images`` by one ``images.apply_jobs`` call, and
+        the rows that got their block are marked present in one executemany.
+        ``images`` must hold an image for every file with a missing row.
+
+        Returns (n_jobs, rejected, consumed, n_left): the rows written,
+        ``rejected`` and ``consumed`` as ``receive_block_data`` gives them,
+        and the rows still missing (0: ``check_temp_files`` reports nothing
+        missing).  Raises what ``receive_block_data`` raises.  Unlike it, a
+        payload whose length is not its row's size is not written and the row
+        stays missing."""
+        import torch
+
+        from . import device as _device
+        from . import wire
+        data = bytes(data)
+        dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        run = torch.frombuffer(bytearray(data), dtype=torch.uint8).to(dev) if data else \
+            torch.empty(0, dtype=torch.uint8, device=dev)
+        digests, sizes, offsets, ok, consumed, stop, _need = wire.receive_block_data_device(run, verify=verify)
+        if stop == wire.SF_WIRE_MALFORMED:
+            raise wire.ProtocolError("Malformed BLOCK_DATA run at byte %d" % consumed)
+        if stop == wire.SF_WIRE_OTHER:
+            raise wire.ProtocolError("Unexpected message in a BLOCK_DATA run (byte %d)" % consumed)
+        rows = self.missing_rows()
+        n = len(rows)
+        base, length = {}, {}
+        for r in rows:
+            if r[2] not in base:
+                base[r[2]] = images.base(r[2]) if r[2] is not None else None
+                length[r[2]] = images.image(r[2]).numel() if r[2] is not None else 0
+            if base[r[2]] is None:
+                raise KeyError(f"missing row {r[0]} belongs to no file")
+            if r[3] + r[4] > length[r[2]]:
+                raise ValueError(f"row [{r[3]}, {r[3] + r[4]}) ends past the {length[r[2]]} bytes of {r[2]}")
+        row_sizes = torch.from_numpy(np.fromiter((r[4] for r in rows), np.uint32, n).view(np.int32)).to(dev)
+        row_dst = torch.from_numpy(np.fromiter((base[r[2]] + r[3] for r in rows), np.int64, n)).to(dev)
+        present = torch.zeros(n, dtype=torch.uint8, device=dev)
+        src, dst, szs, job_rows, _msgs, _uses, n_left, _mismatch = _device.place_block_data(
+            self._digest_table(rows, dev), row_sizes, row_dst, present, digests, sizes, offsets, ok)
+        images.apply_jobs(run, src, dst, szs)
+        self.begin()
+        self.db.executemany("UPDATE blocks SET present = 1 WHERE rowid = ?;",
+                            ((rows[k][0],) for k in job_rows.cpu().tolist()))
+        rejected = [HashDigest(bytes(d)) for d, good in zip(digests.cpu().numpy(), ok.cpu().numpy()) if not good] \
+            if verify else []
+        return int(job_rows.numel()), rejected, consumed, n_left
+
     def get_file(self, name) -> Optional[Tuple[int, DateTimeUtc, Optional[HashDigest]]]:
         row = self.db.execute(
             "SELECT file_id, modified, blocks_hash FROM files WHERE name = ? AND temporary = 0;",
