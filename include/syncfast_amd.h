@@ -275,7 +275,9 @@ enum {
     SF_WIRE_INCOMPLETE = 1, /* the start of a message: more bytes could complete it */
     SF_WIRE_OTHER = 2,      /* a complete command line of another message (FILE_END, ...):
                                the caller's parser takes over there */
-    SF_WIRE_MALFORMED = 3   /* the reference parser would raise there */
+    SF_WIRE_MALFORMED = 3,  /* the reference parser would raise there */
+    SF_WIRE_UNEXPECTED = 4  /* sf_receive_files_device only: a whole, valid FILE_START, FILE_BLOCK or
+                               FILE_END that the sink's state does not take there */
 };
 
 /* The inverse of sf_wire_blocks_device: the longest prefix of whole FILE_BLOCK
@@ -328,6 +330,75 @@ int sf_receive_blocks_device(const sf_block_set *set /* NULL: no lookup */, cons
 int sf_receive_blocks_buffer(const sf_block_set *set, const void *wire /* host */, uint64_t n_bytes,
                              uint64_t base_offset, sf_block_sig *out, int64_t *src_rows, uint64_t cap,
                              uint64_t *n_out, uint64_t *consumed, int *stop, uint64_t *end_offset);
+
+/* The sink's whole GetFiles state (src/sync/fs.rs:449-500) for a buffer of
+ * MANY files in one call.  The destination sends every GET_FILE at once, so
+ * the source answers back to back and one received buffer holds
+ *   FILE_START\n<name>\n (FILE_BLOCK\n<20 B>\n<size>\n)* FILE_END\n FILE_START\n...
+ * beginning and ending anywhere.  d_wire[0, n_bytes) is parsed as the
+ * reference parser reads it (FILE_START: a name of 0 to 100 bytes holding no
+ * newline, read_line(FILENAME_MAX) of proto.rs:271-290 -- 100 name bytes or
+ * more with no newline among the first 101 are "Unterminated filename", not a
+ * prefix; FILE_BLOCK as sf_wire_parse_blocks_device; FILE_END) and accepted in
+ * the sink's order: FILE_START only with no file open, FILE_BLOCK and FILE_END
+ * only with one; `open` != 0 says that a file was open when the buffer began.
+ *
+ * Sections: the files of the call, numbered in stream order.  With open != 0
+ * section 0 is the file carried in (its FILE_START came in an earlier call):
+ * d_file_name_at[0] = UINT64_MAX, d_file_name_len[0] = 0, its offsets start at
+ * base_offset, and it exists even with no message at all (*n_files >= 1).
+ * Every FILE_START opens the next section f: its name is the
+ * d_file_name_len[f] bytes at d_wire + d_file_name_at[f] (bytes as they came:
+ * String::from_utf8 and get_temp_file stay with the caller).  d_file_first[f]
+ * = the section's first block; d_file_first has *n_files + 1 entries, the
+ * last = *n_blocks (an empty file: first[f] == first[f + 1], size 0).
+ * d_file_size[f] = the running offset at the section's end: what FILE_END
+ * passes to set_file_size_and_compute_blocks_hash (fs.rs:480).  Every section
+ * but the last is closed; the last is closed exactly when *open_out == 0.
+ * Blocks: block i is digest d_digests + 20 * i, d_sizes[i], section
+ * d_block_file[i], d_offsets[i] = the running offset of fs.rs:477 within its
+ * section (restarted at every FILE_START; + base_offset in a section carried
+ * in) and, with a set, d_rows[i] = sf_block_set_lookup's row or -1 (one lookup
+ * of all digests of all files).
+ *
+ * *consumed = the bytes of the accepted messages, *stop = SF_WIRE_* for what
+ * stands at d_wire + *consumed: the other six commands' complete line is
+ * SF_WIRE_OTHER whatever follows it, a whole message of the three kinds that
+ * the sink's state does not take is SF_WIRE_UNEXPECTED.  *end_offset = the
+ * running offset of the last section (base_offset unchanged when there is no
+ * section).  A buffer that arrives in pieces is continued with the unconsumed
+ * tail + the new bytes, open = *open_out and base_offset = *end_offset.
+ *
+ * Every byte position is tested for a whole message in parallel, and the
+ * positions that chain from byte 0 in the sink's order are the messages
+ * (sf_recv_files.hip).  A message start inside the last
+ * chained message -- a digest that spells a tag, a file named "x/FILE_END", a
+ * name that ends in "FILE_START" in front of a FILE_BLOCK -- is noticed, and
+ * the buffer is then copied back and parsed on the host, serially: the result
+ * is the reference's for any input.
+ *
+ * SF_ENOSPC with both needs in *n_blocks / *n_files (and *consumed, *stop,
+ * *open_out) when block_cap or file_cap is too small or one of the
+ * outputs but d_rows is NULL (a query: nothing is written then).  With a capacity too small, the first min(need, cap) entries of
+ * d_digests, d_sizes and d_block_file and of d_file_name_at, d_file_name_len
+ * and d_file_first (without its last entry) are written; no offset, no file
+ * size, no row.  Nothing past block_cap / file_cap entries (file_cap + 1 of
+ * d_file_first) is ever written.  A size above 2^32 - 1 gives SF_ERANGE.
+ * SF_EINVAL before any device call: a NULL result pointer, a NULL buffer with
+ * n_bytes > 0, n_bytes > 2^35 (the files and the blocks before a position are
+ * counted in the two halves of one 64-bit scan), d_rows NULL with a set;
+ * d_digests, d_sizes, d_block_file, d_file_name_len not 4-B aligned;
+ * d_offsets, d_rows, d_file_name_at, d_file_first, d_file_size not 8-B
+ * aligned.  n_bytes == 0 launches nothing, needs no device, writes no entry
+ * and hands the state back: *open_out = (open != 0), *end_offset =
+ * base_offset, *n_files = that.  d_wire needs no alignment.
+ * Scratch: n_bytes * 0.8 at the most from the library's stream-ordered pool.  Blocking. */
+int sf_receive_files_device(const sf_block_set *set /* NULL: no lookup */, const void *d_wire, uint64_t n_bytes,
+                            int open, uint64_t base_offset, void *d_digests /* 4-B aligned */, uint32_t *d_sizes,
+                            uint64_t *d_offsets, int64_t *d_rows, uint32_t *d_block_file, uint64_t block_cap,
+                            uint64_t *d_file_name_at, uint32_t *d_file_name_len, uint64_t *d_file_first,
+                            uint64_t *d_file_size, uint64_t file_cap, uint64_t *n_blocks, uint64_t *n_files,
+                            uint64_t *consumed, int *stop, int *open_out, uint64_t *end_offset, void *stream);
 
 /* ------------------------------ receiving a BLOCK_DATA run, on the device ---- */
 

@@ -88,6 +88,14 @@ int sf_test_zpaq_device_stats(uint64_t out[4]);
  * out[3] reserved (0).  Host only; not synchronised with calls in flight. */
 int sf_test_wire_parse_stats(uint64_t out[4]);
 
+/* What the last sf_receive_files_device of this process did: out[0] the
+ * candidate positions the device found (0 when the parse was forced to the
+ * host), out[1] the accepted messages of all three kinds, out[2] 1 if the
+ * host fallback ran (a message start inside the last chained message, or
+ * SF_TEST_WIRE_PARSE_HOST), out[3] reserved (0).  Host only; not synchronised
+ * with calls in flight. */
+int sf_test_recv_files_stats(uint64_t out[4]);
+
 /* What the last BLOCK_DATA parse of this process did (sf_receive_block_data_device
  * / _buffer): out[0] the candidate positions the device found, out[1] the
  * messages, out[2] 1 if the host walked the candidate list (a candidate inside

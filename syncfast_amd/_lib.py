@@ -26,6 +26,8 @@ SF_ETIMEDOUT = -110
 
 # Why a FILE_BLOCK parse stopped (sf_wire_parse_blocks_device)
 SF_WIRE_END, SF_WIRE_INCOMPLETE, SF_WIRE_OTHER, SF_WIRE_MALFORMED = 0, 1, 2, 3
+# sf_receive_files_device only: a whole message the sink's state does not take
+SF_WIRE_UNEXPECTED = 4
 
 HASH_DIGEST_LEN = 20
 MAX_BLOCK_SIZE = 32 << 20
@@ -117,6 +119,8 @@ def _table():
         "sf_wire_parse_blocks_device": (i32, [vp, u64, vp, vp, u64, pu64, pu64, pint, vp]),
         "sf_receive_blocks_device": (i32, [vp, vp, u64, u64, vp, vp, vp, vp, u64, pu64, pu64, pint, pu64, vp]),
         "sf_receive_blocks_buffer": (i32, [vp, vp, u64, u64, sig, vp, u64, pu64, pu64, pint, pu64]),
+        "sf_receive_files_device": (i32, [vp, vp, u64, i32, u64, vp, vp, vp, vp, vp, u64, vp, vp, vp, vp, u64, pu64, pu64,
+                                          pu64, pint, pint, pu64, vp]),
         "sf_receive_block_data_device": (i32, [vp, u64, vp, vp, vp, vp, u64, pu64, pu64, pint, pu64, pu64, vp]),
         "sf_receive_block_data_buffer": (i32, [vp, u64, sig, vp, u64, pu64, pu64, pint, pu64, pu64]),
         "sf_wire_block_data_device": (i32, [vp, u64, vp, vp, vp, u64, P(vp), vp]),
@@ -172,6 +176,7 @@ def _table():
         "sf_test_xcd_litmus": (i32, [i32, pu32]),
         "sf_test_zpaq_device_stats": (i32, [vp]),
         "sf_test_wire_parse_stats": (i32, [vp]),
+        "sf_test_recv_files_stats": (i32, [vp]),
         "sf_test_block_data_stats": (i32, [vp]),
         "sf_test_copy_stats": (i32, [vp]),
     }

@@ -31,6 +31,10 @@
 //   sf_recv_data.hip  BLOCK_DATA runs parsed and their payloads verified on
 //                 the device (its own kernels; the rules are sf_wire_data.hpp;
 //                 what the two parsers share is sf_recv_scan.hpp).
+//   sf_recv_files.hip  a whole GetFiles stream -- many files' FILE_START,
+//                 FILE_BLOCK and FILE_END in one buffer -- parsed, offset and
+//                 looked up in one call (its own kernels; the rules are
+//                 sf_wire_files.hpp; the scan is sf_recv_scan.hpp's).
 //   sf_copy.hip   the block copy kernel that assembles the incoming files in
 //                 HBM (its own kernels; the arithmetic is sf_copy_plan.hpp).
 //   sf_send.hip   BLOCK_DATA runs built on the device, and a GET_BLOCK run

@@ -20,12 +20,12 @@ from __future__ import annotations
 import contextlib
 import ctypes
 import math
-from typing import Optional, Sequence, Tuple
+from typing import NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
-from ._lib import SF_ERANGE, ChainJob, FileDesc, SfError, check, lib, num_blocks, retry_enospc
+from ._lib import SF_ENOSPC, SF_ERANGE, ChainJob, FileDesc, SfError, check, lib, num_blocks, retry_enospc
 
 __all__ = [
     "num_blocks", "index_device", "index_device_blocks", "index_device_batch",
@@ -406,6 +406,33 @@ def _receive_outputs(run: torch.Tensor, lookup: bool):
     return cap, digests, sizes, offsets, torch.empty(cap, dtype=torch.int64, device=run.device)
 
 
+class FilesReceived(NamedTuple):
+    """What ``BlockSet.receive_files`` returns (sf_receive_files_device).
+    Blocks, one row per FILE_BLOCK in stream order: ``digests`` uint8[n, 20],
+    ``sizes`` uint32[n], ``offsets`` int64[n] within the block's file, ``rows``
+    int64[n] as ``lookup`` gives them, ``block_file`` int32[n] the block's
+    section.  Sections, one row per file of the call in stream order:
+    ``name_at`` int64[m] / ``name_len`` int32[m] the name's bytes in the run
+    (-1 / 0 for a file carried in), ``file_first`` int64[m + 1] the section's
+    first block (the last entry = n), ``file_size`` int64[m] the running
+    offset at the section's end.  ``consumed`` / ``stop`` as
+    wire.parse_blocks_device (``stop`` may be SF_WIRE_UNEXPECTED), ``open`` /
+    ``end_offset`` the state to carry into the next call."""
+    digests: torch.Tensor
+    sizes: torch.Tensor
+    offsets: torch.Tensor
+    rows: torch.Tensor
+    block_file: torch.Tensor
+    name_at: torch.Tensor
+    name_len: torch.Tensor
+    file_first: torch.Tensor
+    file_size: torch.Tensor
+    consumed: int
+    stop: int
+    open: bool
+    end_offset: int
+
+
 class BlockSet:
     """The receiving side's block lookup, on the device (sf_block_set_*).
 
@@ -479,6 +506,55 @@ class BlockSet:
         k = n.value
         return (digests[:k], sizes[:k].view(torch.uint32), offsets[:k], rows[:k], consumed.value, stop.value,
                 end.value)
+
+    def receive_files(self, run: torch.Tensor, open: bool = False, base_offset: int = 0) -> FilesReceived:
+        """A whole GetFiles stream as the destination receives it, in one call
+        (sf_receive_files_device): ``run`` (a flat uint8 HBM tensor) holds any
+        number of files -- FILE_START, FILE_BLOCKs, FILE_END, back to back,
+        beginning and ending anywhere -- and is parsed on the device as
+        ``wire.Parser`` reads it and accepted in the sink's order
+        (src/sync/fs.rs:449-500); every block gets its file, its running
+        offset within that file and its lookup in this set.  ``open`` /
+        ``base_offset``: a file was open when the run began (section 0 of the
+        result, without a name) and its running offset.  A run that arrives in
+        pieces is continued with ``run[consumed:]`` + the new bytes and the
+        returned ``open`` / ``end_offset``.  The outputs are sized by a guess
+        and the call is repeated once with the needs it reported when the
+        guess was short.  Blocking."""
+        _require_device(run, "run", torch.uint8, self.table.device)
+        if run.dim() != 1:
+            raise ValueError("run must be a flat uint8 tensor")
+        if not self._h:
+            raise ValueError("BlockSet is closed")
+        dev, nbytes = self.table.device, run.numel()
+        nb, nf, consumed, end = (ctypes.c_uint64(0) for _ in range(4))
+        stop, open_out = ctypes.c_int(0), ctypes.c_int(0)
+        bcap, fcap = nbytes // 36 + 64, nbytes // 1024 + 64  # messages of 37 bytes, files of a few blocks at least
+        with _on(dev, self.stream):
+            for attempt in range(2):
+                e = lambda n, t: torch.empty(n, dtype=t, device=dev)  # noqa: E731
+                digests, sizes, block_file = e((bcap, 20), torch.uint8), e(bcap, torch.int32), e(bcap, torch.int32)
+                offsets, rows = e(bcap, torch.int64), e(bcap, torch.int64)
+                name_at, name_len = e(fcap, torch.int64), e(fcap, torch.int32)
+                first, fsize = e(fcap + 1, torch.int64), e(fcap, torch.int64)
+                rc = lib().sf_receive_files_device(
+                    self._h, _ptr(run), nbytes, int(bool(open)), int(base_offset), digests.data_ptr(), sizes.data_ptr(),
+                    offsets.data_ptr(), rows.data_ptr(), block_file.data_ptr(), bcap, name_at.data_ptr(),
+                    name_len.data_ptr(), first.data_ptr(), fsize.data_ptr(), fcap, ctypes.byref(nb), ctypes.byref(nf),
+                    ctypes.byref(consumed), ctypes.byref(stop), ctypes.byref(open_out), ctypes.byref(end),
+                    _stream_ptr(self.table, self.stream))
+                if rc != SF_ENOSPC or attempt:
+                    break
+                bcap, fcap = max(bcap, nb.value), max(fcap, nf.value)
+            check(rc, "sf_receive_files_device")
+            b, f = nb.value, nf.value
+            if nbytes == 0 and f:  # nothing ran: the section carried in, as the library describes it
+                name_at[0], name_len[0], first[0], fsize[0] = -1, 0, 0, int(base_offset)
+            if nbytes == 0:
+                first[f] = 0
+        return FilesReceived(digests[:b], sizes[:b].view(torch.uint32), offsets[:b], rows[:b], block_file[:b],
+                             name_at[:f], name_len[:f], first[:f + 1], fsize[:f], consumed.value, stop.value,
+                             bool(open_out.value), end.value)
 
     def serve(self, requests: torch.Tensor, src: torch.Tensor, row_offsets: torch.Tensor, row_sizes: torch.Tensor):
         """The source's answer to a received run of GET_BLOCK requests, in one

@@ -451,6 +451,85 @@ class Index:
         return [(PurePath(rows[r][2]), int(rows[r][3]), int(o), int(s))
                 for o, s, r in zip(offsets, sizes, found) if r >= 0]
 
+    def receive_files(self, data, device=None, open_file=None):
+        """The sink's GetFiles state (src/sync/fs.rs:449-500) for a buffer of
+        MANY files in one device call.  ``data``: received bytes as the wire
+        delivers them -- FILE_START, FILE_BLOCKs and FILE_END of one file after
+        the other, beginning and ending anywhere.  ``open_file``: the carry of
+        the call before, (file_id, offset) of the file that was open when
+        ``data`` began, or None.
+
+        One upload, one table (``_lookup_table``), one ``BlockSet`` and one
+        ``BlockSet.receive_files`` parse the buffer, give every block its file
+        and running offset and look it up.  The names are taken from ``data``
+        by the returned spans, decoded as UTF-8 (a bad encoding raises
+        wire.ProtocolError, Error::BadFilenameEncoding) and resolved with
+        ``get_temp_file`` (an unknown name raises SyncfastError, as
+        fs.rs:455-456 does).  Then ONE executemany inserts the rows of all
+        files -- present = 1 where the lookup found a row (add_block), else 0
+        (add_missing_block) -- and ``set_file_size_and_compute_blocks_hash``
+        runs for every closed file, in stream order.
+
+        One lookup against the table at entry is what the reference's
+        message-by-message loop gives: get_block returns the first present
+        row in (hash, rowid) order, and every row added during the loop has a
+        higher rowid than every row of the table at entry -- so a hash found
+        at entry is found in the same row later, and a hash not found at entry
+        is only ever added as missing.
+
+        Returns (copies, consumed, carry).  copies: {temp file name: [(from_name,
+        from_offset, to_offset, size)]} for every file of the call, each list
+        in ``receive_file_blocks``' format (the blocks recorded as present are
+        NOT written by this call).  consumed: the bytes of the accepted
+        messages; an incomplete message after them is the caller's to keep for
+        the next call.  carry: (file_id, offset) of the file still open after
+        them, or None.  Bytes the parser raises on, a message the sink's state
+        does not take, or another command right after the accepted messages
+        raise wire.ProtocolError; in every raising case nothing is written."""
+        import torch
+
+        from . import wire
+        from .device import BlockSet
+        data = bytes(data)
+        rows, table, present = self._lookup_table()
+        dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        run = torch.frombuffer(bytearray(data), dtype=torch.uint8).to(dev) if data else \
+            torch.empty(0, dtype=torch.uint8, device=dev)
+        with BlockSet(torch.from_numpy(table.copy()).to(dev), torch.from_numpy(present).to(dev)) as bset:
+            r = bset.receive_files(run, open=open_file is not None, base_offset=open_file[1] if open_file else 0)
+            digests, sizes, offsets, found, block_file, name_at, name_len, _first, file_size = (
+                t.cpu().numpy() for t in r[:9])
+        if r.stop == wire.SF_WIRE_MALFORMED:
+            raise wire.ProtocolError("Malformed GetFiles stream at byte %d" % r.consumed)
+        if r.stop in (wire.SF_WIRE_UNEXPECTED, wire.SF_WIRE_OTHER):
+            raise wire.ProtocolError("Unexpected message from source (byte %d)" % r.consumed)
+        ids = []
+        for at, n in zip(name_at.tolist(), name_len.tolist()):
+            if at < 0:  # the file carried in
+                ids.append(int(open_file[0]))
+                continue
+            try:
+                name = data[at:at + n].decode("utf-8")
+            except UnicodeDecodeError:
+                raise wire.ProtocolError("Bad filename encoding (byte %d)" % at) from None
+            temp = self.get_temp_file(PurePath(name))
+            if temp is None:
+                raise SyncfastError("Unknown file %r" % name)
+            ids.append(temp[0])
+        names = [self.get_file_name(i) for i in ids]
+        copies = {name: [] for name in names}
+        self.begin()
+        self.db.executemany(
+            "INSERT INTO blocks(hash, file_id, offset, size, present) VALUES(?, ?, ?, ?, ?);",
+            ((bytes(d).hex(), ids[f], int(o), int(s), int(q >= 0))
+             for d, f, o, s, q in zip(digests, block_file, offsets, sizes, found)))
+        for f in range(len(ids) - 1 if r.open else len(ids)):
+            self.set_file_size_and_compute_blocks_hash(ids[f], int(file_size[f]))
+        for f, o, s, q in zip(block_file, offsets, sizes, found):
+            if q >= 0:
+                copies[names[f]].append((PurePath(rows[q][2]), int(rows[q][3]), int(o), int(s)))
+        return copies, r.consumed, ((ids[-1], r.end_offset) if r.open else None)
+
     def apply_block_data(self, digests, sizes, data_offsets, ok=None):
         """The database half of ``receive_block_data``, from the parsed arrays
         (no GPU): for each message in order whose payload verified (``ok``

@@ -19,7 +19,7 @@ import re
 from typing import List, Tuple
 
 from ._lib import (SF_ENOSPC, SF_OK, SF_WIRE_END, SF_WIRE_INCOMPLETE, SF_WIRE_MALFORMED,  # noqa: F401
-                   SF_WIRE_OTHER, check, lib)
+                   SF_WIRE_OTHER, SF_WIRE_UNEXPECTED, check, lib)
 from .digest import HashDigest
 
 
@@ -239,6 +239,15 @@ def parse_stats():
     host fallback ran, 0) of this process's last FILE_BLOCK parse."""
     out = (ctypes.c_uint64 * 4)()
     check(lib().sf_test_wire_parse_stats(out), "sf_test_wire_parse_stats")
+    return tuple(int(v) for v in out)
+
+
+def recv_files_stats():
+    """Test hook (sf_test_recv_files_stats): (candidates, accepted messages,
+    whether the host fallback ran, 0) of this process's last
+    ``device.BlockSet.receive_files`` / sf_receive_files_device."""
+    out = (ctypes.c_uint64 * 4)()
+    check(lib().sf_test_recv_files_stats(out), "sf_test_recv_files_stats")
     return tuple(int(v) for v in out)
 
 
