@@ -16,6 +16,7 @@
 #include <algorithm>
 
 #include "sf_block_hash.hpp"
+#include "sf_device.hpp"
 
 namespace sf {
 
@@ -139,22 +140,17 @@ int launch_fixed(const void* d_data, uint64_t len, uint32_t bs, uint64_t nblocks
   const sf::PadSchedule pad = pad_schedule(bs);
   const uint8_t* d = static_cast<const uint8_t*>(d_data);
   uint8_t* o = static_cast<uint8_t*>(d_digests);
-  clear_stale_error();
   if (weak)  // opt-in fused Adler-32 (a separate instantiation; the default kernel is unchanged)
-    hipLaunchKernelGGL((sf::sha1_fixed_kernel<kTile, 1, true>), dim3(grid), dim3(sf::kThreads), 0, stream, d, len, bs,
-                       nblocks, o, pad, weak);
-  else
-    hipLaunchKernelGGL((sf::sha1_fixed_kernel<kTile, 1>), dim3(grid), dim3(sf::kThreads), 0, stream, d, len, bs,
-                       nblocks, o, pad, nullptr);
-  return hip_err(hipGetLastError());
+    return launch(sf::sha1_fixed_kernel<kTile, 1, true>, dim3(grid), dim3(sf::kThreads), stream, d, len, bs, nblocks, o,
+                  pad, weak);
+  return launch(sf::sha1_fixed_kernel<kTile, 1>, dim3(grid), dim3(sf::kThreads), stream, d, len, bs, nblocks, o, pad,
+                nullptr);
 }
 
 int launch_chain_plain(const uint8_t* d_runs, uint64_t run_stride, uint32_t nfiles, uint32_t run_len,
                        uint8_t* d_hashes, hipStream_t stream) {
-  clear_stale_error();
-  hipLaunchKernelGGL(sf::sha1_chain_kernel, dim3((unsigned)ceil_div(nfiles, 64)), dim3(64), 0, stream, d_runs,
-                     run_stride, nfiles, run_len, d_hashes);
-  return hip_err(hipGetLastError());
+  return launch(sf::sha1_chain_kernel, dim3((unsigned)ceil_div(nfiles, 64)), dim3(64), stream, d_runs, run_stride,
+                nfiles, run_len, d_hashes);
 }
 
 // The fixed-tiling entry point and its weak form: d_weak is asked for and
@@ -244,10 +240,8 @@ int sf_fill_splitmix_device(void* d_out, uint64_t len, uint64_t seed, uint64_t s
   if (!d_out) return SF_EINVAL;
   const uint64_t nvec = len / 16 + 1;
   const unsigned grid = (unsigned)std::min<uint64_t>(ceil_div(nvec, 256), 65536);
-  clear_stale_error();
-  hipLaunchKernelGGL(sf::fill_splitmix_kernel, dim3(grid), dim3(256), 0, as_stream(stream),
-                     static_cast<uint8_t*>(d_out), len, seed, start);
-  return hip_err(hipGetLastError());
+  return launch(sf::fill_splitmix_kernel, dim3(grid), dim3(256), as_stream(stream), static_cast<uint8_t*>(d_out), len,
+                seed, start);
 }
 
 }  // extern "C"

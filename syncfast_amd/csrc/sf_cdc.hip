@@ -54,11 +54,10 @@
 #include <sys/stat.h>
 #include <unistd.h>
 
-#include <rocprim/device/device_scan.hpp>
-
 #include <memory>
 
 #include "host_sha1.h"
+#include "sf_device.hpp"
 #include "sf_launch.hpp"
 #include "sf_stage.hpp"
 #include "sf_zpaq_step.hpp"
@@ -318,7 +317,7 @@ __global__ void __launch_bounds__(256) zpaq_emit_kernel(const uint32_t* __restri
   }
 }
 
-std::atomic<uint64_t> g_last_stats[4];  // sf_test_zpaq_device_stats
+sfi::Stats4 g_last_stats;  // sf_test_zpaq_device_stats
 
 inline uint64_t gcd64(uint64_t a, uint64_t b) {
   while (b) {
@@ -347,54 +346,45 @@ int zpaq_cut_plan(const uint8_t* d_data, uint64_t len, uint32_t bits, uint32_t m
   const uint64_t L = zpaq_segment_len(max_size), nseg = ceil_div(len, L), nwords = ceil_div(len, 32);
   if (ceil_div(nseg, kLanes) > 0x7FFFFFFFull) return SF_EINVAL;
   size_t tmp = 0;
-  uint64_t* nul = nullptr;
-  if (rocprim::inclusive_scan(nullptr, tmp, nul, nul, (size_t)nseg, rocprim::plus<uint64_t>(), s) != hipSuccess) {
-    (void)hipGetLastError();
-    return SF_ENODEV;
-  }
-  const size_t wb = align256(nwords * 4), sb = align256(nseg * 8);
-  uint8_t* ws = nullptr;
-  const int arc = stream_alloc(reinterpret_cast<void**>(&ws), 2 * wb + 7 * sb + 256 + tmp + 8, s);
-  if (arc != SF_OK) return arc;
-  p->ws = ws;
-  uint32_t* spec = reinterpret_cast<uint32_t*>(ws);
-  uint32_t* cur = reinterpret_cast<uint32_t*>(ws + wb);
-  uint64_t* seg = reinterpret_cast<uint64_t*>(ws + 2 * wb);
-  const size_t sw = sb / 8;
-  uint64_t *last[2] = {seg, seg + sw}, *lastspec = seg + 2 * sw, *used = seg + 3 * sw, *counts = seg + 4 * sw,
-           *ends = seg + 5 * sw;
-  Counters* ctr = reinterpret_cast<Counters*>(ws + 2 * wb + 7 * sb);
-  void* scan_tmp = ws + 2 * wb + 7 * sb + 256;
+  uint64_t* const nul = nullptr;
+  int rc = scan_inclusive(nullptr, tmp, nul, nul, nseg, s);
+  if (rc != SF_OK) return rc;
+  // two bitmaps of the cuts, six lists of one entry per segment, the counters, the scan's
+  ScratchLayout lay;
+  const size_t spec_at = lay.add(nwords * 4), cur_at = lay.add(nwords * 4);
+  size_t seg_at[6];
+  for (size_t& at : seg_at) at = lay.add(nseg * 8);
+  const size_t ctr_at = lay.add(sizeof(Counters));
+  if ((rc = stream_alloc(&p->ws, lay.total() + tmp + 8, s)) != SF_OK) return rc;
+  uint32_t* spec = lay.at<uint32_t>(p->ws, spec_at);
+  uint32_t* cur = lay.at<uint32_t>(p->ws, cur_at);
+  uint64_t* seg[6];
+  for (int k = 0; k < 6; k++) seg[k] = lay.at<uint64_t>(p->ws, seg_at[k]);
+  uint64_t *last[2] = {seg[0], seg[1]}, *lastspec = seg[2], *used = seg[3], *counts = seg[4], *ends = seg[5];
+  Counters* ctr = lay.at<Counters>(p->ws, ctr_at);
   const uint32_t lim = sfz::limit(bits);
   const dim3 grid((unsigned)ceil_div(nseg, kLanes)), block(kLanes);
   SF_HIP(hipMemsetAsync(ctr, 0, sizeof(Counters), s));
-  clear_stale_error();
-  hipLaunchKernelGGL(zpaq_round0_kernel, grid, block, 0, s, d_data, len, L, nseg, lim, max_size, spec, cur, last[0],
-                     lastspec, used);
-  SF_HIP(hipGetLastError());
+  rc = launch(zpaq_round0_kernel, grid, block, s, d_data, len, L, nseg, lim, max_size, spec, cur, last[0], lastspec,
+              used);
+  if (rc != SF_OK) return rc;
   uint64_t rounds = 0;
   int in = 0;
   Counters hc{};
   for (; nseg > 1; rounds++) {
     if (rounds > nseg) return SF_EIO;  // cannot happen: the fixed point is reached in nseg rounds
     SF_HIP(hipMemsetAsync(&ctr->changed, 0, sizeof(uint32_t), s));
-    clear_stale_error();
-    hipLaunchKernelGGL(zpaq_join_kernel, grid, block, 0, s, d_data, len, L, nseg, lim, max_size, spec, cur, last[in],
-                       last[in ^ 1], lastspec, used, ctr);
-    SF_HIP(hipGetLastError());
+    rc = launch(zpaq_join_kernel, grid, block, s, d_data, len, L, nseg, lim, max_size, spec, cur, last[in],
+                last[in ^ 1], lastspec, used, ctr);
+    if (rc != SF_OK) return rc;
     SF_HIP(hipMemcpyAsync(&hc, ctr, sizeof(Counters), hipMemcpyDeviceToHost, s));
     SF_HIP(hipStreamSynchronize(s));
     in ^= 1;
     if (hc.changed == 0) break;
   }
-  const dim3 g256((unsigned)ceil_div(nseg, 256));
-  clear_stale_error();
-  hipLaunchKernelGGL(zpaq_count_kernel, g256, dim3(256), 0, s, cur, len, L, nseg, counts);
-  SF_HIP(hipGetLastError());
-  if (rocprim::inclusive_scan(scan_tmp, tmp, counts, ends, (size_t)nseg, rocprim::plus<uint64_t>(), s) != hipSuccess) {
-    (void)hipGetLastError();
-    return SF_ENODEV;
-  }
+  rc = launch(zpaq_count_kernel, grid256(nseg), dim3(256), s, cur, len, L, nseg, counts);
+  if (rc == SF_OK) rc = scan_inclusive(lay.at<void>(p->ws, lay.total()), tmp, counts, ends, nseg, s);
+  if (rc != SF_OK) return rc;
   uint64_t total = 0;
   SF_HIP(hipMemcpyAsync(&total, ends + nseg - 1, 8, hipMemcpyDeviceToHost, s));
   SF_HIP(hipStreamSynchronize(s));
@@ -405,20 +395,17 @@ int zpaq_cut_plan(const uint8_t* d_data, uint64_t len, uint32_t bits, uint32_t m
   p->cur = cur;
   p->ends = ends;
   p->last = last[in];
-  g_last_stats[0].store(L, std::memory_order_relaxed);
-  g_last_stats[1].store(nseg, std::memory_order_relaxed);
-  g_last_stats[2].store(rounds, std::memory_order_relaxed);
-  g_last_stats[3].store(hc.recut, std::memory_order_relaxed);
+  g_last_stats.set(0, L);
+  g_last_stats.set(1, nseg);
+  g_last_stats.set(2, rounds);
+  g_last_stats.set(3, hc.recut);
   return SF_OK;
 }
 
 // The rows of a plan: p.total entries at d_offsets / d_sizes.  Asynchronous.
 int zpaq_cut_emit(const ZpaqPlan& p, uint64_t* d_offsets, uint32_t* d_sizes, hipStream_t s) {
-  clear_stale_error();
-  hipLaunchKernelGGL(zpaq_emit_kernel, dim3((unsigned)ceil_div(p.nseg, 256)), dim3(256), 0, s,
-                     static_cast<const uint32_t*>(p.cur), p.len, p.L, p.nseg, static_cast<const uint64_t*>(p.ends),
-                     static_cast<const uint64_t*>(p.last), d_offsets, d_sizes);
-  return hip_err(hipGetLastError());
+  return launch(zpaq_emit_kernel, grid256(p.nseg), dim3(256), s, static_cast<const uint32_t*>(p.cur), p.len, p.L,
+                p.nseg, static_cast<const uint64_t*>(p.ends), static_cast<const uint64_t*>(p.last), d_offsets, d_sizes);
 }
 
 void zpaq_cut_free(ZpaqPlan* p, hipStream_t s) {
@@ -590,10 +577,6 @@ int sf_index_fd_zpaq(int fd, const sf_file_stamp* expect, uint32_t bits, uint32_
   return guarded([&] { return index_fd_zpaq_body(fd, expect, bits, max_size, rows, n_out, blocks_hash); });
 }
 
-int sf_test_zpaq_device_stats(uint64_t out[4]) {
-  if (!out) return SF_EINVAL;
-  for (int k = 0; k < 4; k++) out[k] = g_last_stats[k].load(std::memory_order_relaxed);
-  return SF_OK;
-}
+int sf_test_zpaq_device_stats(uint64_t out[4]) { return g_last_stats.read(out); }
 
 }  // extern "C"

@@ -35,10 +35,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <rocprim/device/device_scan.hpp>
-
 #include "sf_copy_plan.hpp"
-#include "sf_internal.hpp"
+#include "sf_device.hpp"
 #include "../../include/syncfast_amd_test.h"
 
 namespace {
@@ -212,31 +210,21 @@ int sfi::copy_blocks(const uint8_t* d_src, uint64_t src_len, uint8_t* d_dst, uin
   int rc = device_state(&dev, &cus, &stats);
   if (rc != SF_OK) return rc;
   size_t tmp = 0;
-  {
-    uint64_t* in = nullptr;
-    if (rocprim::inclusive_scan(nullptr, tmp, in, in, (size_t)n, rocprim::plus<uint64_t>(), s) != hipSuccess) {
-      (void)hipGetLastError();
-      return SF_ENODEV;
-    }
-  }
-  const size_t pb = align256((n + 1) * 8);
+  uint64_t* const nul = nullptr;
+  if ((rc = scan_inclusive(nullptr, tmp, nul, nul, n, s)) != SF_OK) return rc;
+  ScratchLayout L;
+  const size_t p_at = L.add((n + 1) * 8);
   Scratch ws(s);
-  if ((rc = stream_alloc(&ws.p, pb + tmp + 8, s)) != SF_OK) return rc;
-  uint64_t* P = static_cast<uint64_t*>(ws.p);
-  void* scan_tmp = static_cast<uint8_t*>(ws.p) + pb;
+  if ((rc = stream_alloc(&ws.p, L.total() + tmp + 8, s)) != SF_OK) return rc;
+  uint64_t* P = L.at<uint64_t>(ws.p, p_at);
   SF_HIP(hipMemsetAsync(stats, 0, sizeof(DevStats), s));
-  clear_stale_error();
-  hipLaunchKernelGGL(copy_count_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, s, d_src_off, d_dst_off, d_sizes,
-                     d_take, n, src_len, b, dst_len, P, d_status, stats);
-  SF_HIP(hipGetLastError());
-  if (rocprim::inclusive_scan(scan_tmp, tmp, P + 1, P + 1, (size_t)n, rocprim::plus<uint64_t>(), s) != hipSuccess) {
-    (void)hipGetLastError();
-    return SF_ENODEV;
-  }
-  clear_stale_error();
-  hipLaunchKernelGGL(copy_tiles_kernel, dim3((unsigned)cus * kBlocksPerCU), dim3(64 * kWavesPerBlock), 0, s, d_src,
-                     src_len, d_dst, d_src_off, d_dst_off, d_sizes, P, n, stats);
-  SF_HIP(hipGetLastError());
+  rc = launch(copy_count_kernel, grid256(n), dim3(256), s, d_src_off, d_dst_off, d_sizes, d_take, n, src_len, b,
+              dst_len, P, d_status, stats);
+  if (rc == SF_OK) rc = scan_inclusive(L.at<void>(ws.p, L.total()), tmp, P + 1, P + 1, n, s);
+  if (rc == SF_OK)
+    rc = launch(copy_tiles_kernel, dim3((unsigned)cus * kBlocksPerCU), dim3(64 * kWavesPerBlock), s, d_src, src_len,
+                d_dst, d_src_off, d_dst_off, d_sizes, P, n, stats);
+  if (rc != SF_OK) return rc;
   g_copy_launches.store(1, std::memory_order_relaxed);
   g_copy_dev.store(dev, std::memory_order_relaxed);
   return SF_OK;

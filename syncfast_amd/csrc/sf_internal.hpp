@@ -30,7 +30,7 @@
 //                 host parser is sf_wire_parse.hpp);
 //   sf_recv_data.hip  BLOCK_DATA runs parsed and their payloads verified on
 //                 the device (its own kernels; the rules are sf_wire_data.hpp;
-//                 what the two parsers share is sf_recv_scan.hpp).
+//                 what the three parsers share is sf_recv_scan.hpp).
 //   sf_recv_files.hip  a whole GetFiles stream -- many files' FILE_START,
 //                 FILE_BLOCK and FILE_END in one buffer -- parsed, offset and
 //                 looked up in one call (its own kernels; the rules are
@@ -44,6 +44,10 @@
 //                 and a parsed BLOCK_DATA run joined against them into a copy
 //                 list (its own kernels; the rules are sf_want_plan.hpp; the
 //                 lookups are sf_match.hip's).
+// Every .hip file launches its kernels and runs its rocprim scans through
+// sf_device.hpp (launch, grid256, scan_inclusive, scan_exclusive), and divides
+// its scratch with sf_layout.hpp (ScratchLayout, for_pieces: host arithmetic,
+// executed by tests/native/layout.cpp).
 // The .cpp files use only the HIP runtime API (no kernels), so they build
 // with the host compiler.
 #pragma once
@@ -65,6 +69,7 @@
 #include <vector>
 
 #include "../../include/syncfast_amd.h"
+#include "sf_layout.hpp"
 #include "sf_stage.hpp"
 
 // Internal status of the in-place route (never returned through the C-ABI):
@@ -147,14 +152,6 @@ inline int hip_err(hipError_t e) {
   return SF_ENODEV;
 }
 
-// hipGetLastError() answers the last failing HIP call of this thread, whatever
-// it was, until it is read.  A launcher reads it after its launch, so it first
-// clears what an earlier call left there -- one of ours whose status is
-// ignored on purpose (hipHostUnregister in cleanup, an attribute probe), or
-// the caller's, or another library's on the same thread -- which would
-// otherwise be reported as the launch's failure (SF_ENODEV from a good launch).
-inline void clear_stale_error() { (void)hipGetLastError(); }
-
 inline uint64_t ceil_div(uint64_t a, uint64_t b) { return (a + b - 1) / b; }
 
 // Whether an output pointer breaks the alignment include/syncfast_amd.h states
@@ -180,8 +177,32 @@ struct Scratch {
   Scratch(const Scratch&) = delete;
   Scratch& operator=(const Scratch&) = delete;
 };
-// The parts of one allocation start on 256-byte boundaries.
-inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+// The life of a run (sf_send.hip), for the entry points that build one:
+// the empty run (no device, no bytes, no event); a run of n_bytes /
+// n_messages on the current device, its bytes allocated on s and its event
+// created (*run stays NULL on failure); and the end of the build, rc being
+// what the build returned so far: the event is recorded on s and *out = run,
+// or on any error the run (which may be NULL) is given back and the error
+// returned.
+sf_wire_run* wire_run_empty();
+int wire_run_begin(uint64_t n_bytes, uint64_t n_messages, hipStream_t s, sf_wire_run** run);
+int wire_run_finish(sf_wire_run* run, int rc, hipStream_t s, sf_wire_run** out);
+
+// The four numbers an entry point keeps of its last call for its
+// sf_test_*_stats reader.
+struct Stats4 {
+  std::atomic<uint64_t> v[4];
+  void reset() {
+    for (auto& x : v) x.store(0, std::memory_order_relaxed);
+  }
+  void set(int k, uint64_t x) { v[k].store(x, std::memory_order_relaxed); }
+  int read(uint64_t out[4]) const {
+    if (!out) return SF_EINVAL;
+    for (int k = 0; k < 4; k++) out[k] = v[k].load(std::memory_order_relaxed);
+    return SF_OK;
+  }
+};
 // FILE_BLOCK runs of explicit lists (sf_wire.hip): end offsets of every
 // message (stream-ordered allocation, hipFreeAsync on s), the end offset of
 // every chunk of `per` messages, and messages [first, first + cnt) written

@@ -20,7 +20,7 @@
 // touched by atomic read-modify-writes; every wait is bounded (status 1).
 #include <hip/hip_runtime.h>
 
-#include "sf_internal.hpp"
+#include "sf_device.hpp"
 #include "../../include/syncfast_amd_test.h"
 
 namespace {
@@ -118,11 +118,7 @@ extern "C" int sf_test_xcd_litmus(int mode, uint32_t out[8]) {
   SF_HIP(hipMalloc(reinterpret_cast<void**>(&w), W_WORDS * sizeof(uint32_t)));
   int rc = SF_OK;
   if (hipMemset(w, 0, W_WORDS * sizeof(uint32_t)) != hipSuccess) rc = SF_ENODEV;
-  if (rc == SF_OK) {
-    sfi::clear_stale_error();
-    hipLaunchKernelGGL(xcd_litmus_kernel, dim3(kLitmusWGs), dim3(64), 0, nullptr, w, mode);
-    rc = sfi::hip_err(hipGetLastError());
-  }
+  if (rc == SF_OK) rc = sfi::launch(xcd_litmus_kernel, dim3(kLitmusWGs), dim3(64), nullptr, w, mode);
   if (rc == SF_OK && hipMemcpy(out, w + W_RESULT, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess)
     rc = SF_ENODEV;
   (void)hipFree(w);

@@ -30,7 +30,7 @@
 
 #include <algorithm>
 
-#include "sf_internal.hpp"
+#include "sf_device.hpp"
 
 namespace sfm {
 
@@ -128,12 +128,9 @@ int block_set_build(const void* d_table, const uint8_t* d_present, uint64_t n_ro
   sf_block_set* bs = new sf_block_set{static_cast<const uint8_t*>(d_table), n_rows, nullptr, cap - 1};
   int rc = stream_alloc(reinterpret_cast<void**>(&bs->slots), cap * sizeof(unsigned long long), s);
   if (rc == SF_OK) rc = hip_err(hipMemsetAsync(bs->slots, 0, cap * sizeof(unsigned long long), s));
-  if (rc == SF_OK && n_rows) {
-    sfi::clear_stale_error();
-    hipLaunchKernelGGL(sfm::block_set_insert_kernel, dim3((unsigned)ceil_div(n_rows, 256)), dim3(256), 0, s,
-                       bs->table, d_present, n_rows, bs->slots, bs->mask);
-    rc = hip_err(hipGetLastError());
-  }
+  if (rc == SF_OK && n_rows)
+    rc = launch(sfm::block_set_insert_kernel, grid256(n_rows), dim3(256), s, bs->table, d_present, n_rows, bs->slots,
+                bs->mask);
   if (rc != SF_OK) {
     stream_free(bs->slots, s);
     delete bs;
@@ -161,16 +158,10 @@ int sf_block_set_lookup(const sf_block_set* set, const void* d_query, uint64_t n
   if (reinterpret_cast<uintptr_t>(d_query) & 3u) return SF_EINVAL;
   if (misaligned(d_rows, 8)) return SF_EINVAL;  // one 8-B store per query
   const uint64_t per = 1ull << 31;  // queries per launch (< 2^32 work-items)
-  for (uint64_t q0 = 0; q0 < n_query; q0 += per) {
-    const uint64_t nq = std::min(per, n_query - q0);
-    sfi::clear_stale_error();
-    hipLaunchKernelGGL(sfm::block_set_lookup_kernel, dim3((unsigned)ceil_div(nq, 256)), dim3(256), 0,
-                       as_stream(stream), set->table, set->slots, set->mask,
-                       static_cast<const uint8_t*>(d_query) + q0 * 20, nq, d_rows + q0);
-    const int rc = hip_err(hipGetLastError());
-    if (rc) return rc;
-  }
-  return SF_OK;
+  return for_pieces(n_query, per, [&](uint64_t q0, uint64_t nq) {
+    return launch(sfm::block_set_lookup_kernel, grid256(nq), dim3(256), as_stream(stream), set->table, set->slots,
+                  set->mask, static_cast<const uint8_t*>(d_query) + q0 * 20, nq, d_rows + q0);
+  });
 }
 
 int sf_block_set_free(sf_block_set* set, void* stream) {

@@ -74,16 +74,6 @@ __device__ __forceinline__ uint32_t message_len(const uint8_t* __restrict__ data
   return sfwp::kSizeAt + sfwp::size_field(data + p + sfwp::kSizeAt, n - p - sfwp::kSizeAt, size);
 }
 
-// The 64 bitmap bits from position q on (bits past the bitmap are 0).
-__device__ __forceinline__ unsigned long long bits_from(const unsigned long long* __restrict__ words, uint64_t nw,
-                                                        uint64_t q) {
-  const uint64_t w = q >> 6;
-  const uint32_t s = (uint32_t)(q & 63);
-  unsigned long long v = w < nw ? words[w] >> s : 0ull;
-  if (s && w + 1 < nw) v |= words[w + 1] << (64 - s);
-  return v;
-}
-
 __global__ void __launch_bounds__(256) recv_chain_kernel(const uint8_t* __restrict__ data, uint64_t n,
                                                          const unsigned long long* __restrict__ words,
                                                          const uint64_t* __restrict__ ends, uint64_t nw,
@@ -130,15 +120,7 @@ __global__ void __launch_bounds__(256) recv_extract_kernel(const uint8_t* __rest
   }
 }
 
-struct Widen {
-  __host__ __device__ uint64_t operator()(uint32_t v) const { return (uint64_t)v; }
-};
-
-std::atomic<uint64_t> g_parse_stats[4];  // sf_test_wire_parse_stats
-
-inline void reset_stats() {
-  for (auto& v : g_parse_stats) v.store(0, std::memory_order_relaxed);
-}
+sfi::Stats4 g_parse_stats;  // sf_test_wire_parse_stats
 
 }  // namespace
 
@@ -176,8 +158,8 @@ int parse_on_host(const uint8_t* d_wire, const uint8_t* h_wire, uint64_t n, uint
   bool too_large = false;
   sfwp::parse_run(h_wire, n, static_cast<uint8_t*>(pdig), static_cast<uint32_t*>(psz), most, &out->count,
                   &out->consumed, &out->stop, &too_large);
-  g_parse_stats[1].store(out->count, std::memory_order_relaxed);
-  g_parse_stats[2].store(1, std::memory_order_relaxed);
+  g_parse_stats.set(1, out->count);
+  g_parse_stats.set(2, 1);
   if (too_large) return SF_ERANGE;
   const uint64_t up = std::min(out->count, cap);
   if (up) {
@@ -194,24 +176,22 @@ int parse_run_device(const uint8_t* d_wire, const uint8_t* h_wire, uint64_t n, u
                      uint64_t cap, Parsed* out, hipStream_t s, HostLease* lease) {
   if (knob(K_TEST_WIRE_PARSE_HOST) == 1) return parse_on_host(d_wire, h_wire, n, d_digests, d_sizes, cap, out, s, lease);
   Scan sc(s);
-  const int rc = scan_candidates<BlockRules>(d_wire, n, s, &sc);
+  int rc = scan_candidates<BlockRules>(d_wire, n, s, &sc);
   if (rc != SF_OK) return rc;
   Result* res = static_cast<Result*>(sc.result);
-  const dim3 gw((unsigned)ceil_div(sc.nw, 256));
-  clear_stale_error();
-  hipLaunchKernelGGL(recv_chain_kernel, gw, dim3(256), 0, s, d_wire, n, sc.words, sc.ends, sc.nw, res);
-  SF_HIP(hipGetLastError());
-  clear_stale_error();
-  hipLaunchKernelGGL(recv_extract_kernel, gw, dim3(256), 0, s, d_wire, n, sc.words, sc.ends, sc.nw,
-                     reinterpret_cast<uint32_t*>(d_digests), d_sizes, cap, res);
-  SF_HIP(hipGetLastError());
+  const dim3 gw = grid256(sc.nw);
+  rc = launch(recv_chain_kernel, gw, dim3(256), s, d_wire, n, sc.words, sc.ends, sc.nw, res);
+  if (rc == SF_OK)
+    rc = launch(recv_extract_kernel, gw, dim3(256), s, d_wire, n, sc.words, sc.ends, sc.nw,
+                reinterpret_cast<uint32_t*>(d_digests), d_sizes, cap, res);
+  if (rc != SF_OK) return rc;
   Result h{};
   SF_HIP(hipMemcpyAsync(&h, res, sizeof(Result), hipMemcpyDeviceToHost, s));
   SF_HIP(hipStreamSynchronize(s));
-  g_parse_stats[0].store(h.cand, std::memory_order_relaxed);
+  g_parse_stats.set(0, h.cand);
   if (h.msgs && !(h.first_bad & 1ull))  // a candidate inside the last chained message
     return parse_on_host(d_wire, h_wire, n, d_digests, d_sizes, cap, out, s, lease);
-  g_parse_stats[1].store(h.msgs, std::memory_order_relaxed);
+  g_parse_stats.set(1, h.msgs);
   if (h.too_large) return SF_ERANGE;
   out->count = h.msgs;
   out->consumed = h.end;
@@ -236,7 +216,7 @@ int parse_run_device(const uint8_t* d_wire, const uint8_t* h_wire, uint64_t n, u
 
 int parse_blocks_device(const void* d_wire, uint64_t n_bytes, void* d_digests, uint32_t* d_sizes, uint64_t cap,
                         uint64_t* n_out, uint64_t* consumed, int* stop, hipStream_t s) {
-  reset_stats();
+  g_parse_stats.reset();
   if (n_out) *n_out = 0;
   if (consumed) *consumed = 0;
   if (stop) *stop = SF_WIRE_END;
@@ -269,7 +249,7 @@ struct ReceiveArgs {
 };
 
 int check_receive_args(const ReceiveArgs& a, const void* wire, uint64_t n_bytes) {
-  reset_stats();
+  g_parse_stats.reset();
   if (a.n_out) *a.n_out = 0;
   if (a.consumed) *a.consumed = 0;
   if (a.stop) *a.stop = SF_WIRE_END;
@@ -295,18 +275,10 @@ int receive_device(const ReceiveArgs& a, const uint8_t* d_wire, const uint8_t* h
   // d_offsets[i] = base_offset + sizes[0] + ... + sizes[i - 1], in 64 bits
   auto in = rocprim::make_transform_iterator(a.d_sizes, Widen());
   size_t tmp = 0;
-  if (rocprim::exclusive_scan(nullptr, tmp, in, a.d_offsets, (uint64_t)a.base_offset, (size_t)p.count,
-                              rocprim::plus<uint64_t>(), s) != hipSuccess) {
-    (void)hipGetLastError();
-    return SF_ENODEV;
-  }
+  if ((rc = scan_exclusive(nullptr, tmp, in, a.d_offsets, a.base_offset, p.count, s)) != SF_OK) return rc;
   Scratch ws(s);
   if ((rc = stream_alloc(&ws.p, tmp + 8, s)) != SF_OK) return rc;
-  if (rocprim::exclusive_scan(ws.p, tmp, in, a.d_offsets, (uint64_t)a.base_offset, (size_t)p.count,
-                              rocprim::plus<uint64_t>(), s) != hipSuccess) {
-    (void)hipGetLastError();
-    return SF_ENODEV;
-  }
+  if ((rc = scan_exclusive(ws.p, tmp, in, a.d_offsets, a.base_offset, p.count, s)) != SF_OK) return rc;
   if (a.set && (rc = sf_block_set_lookup(a.set, a.d_digests, p.count, a.d_rows, s)) != SF_OK) return rc;
   uint64_t last_off = 0;
   uint32_t last_size = 0;
@@ -397,10 +369,6 @@ int sf_receive_blocks_buffer(const sf_block_set* set, const void* wire, uint64_t
   });
 }
 
-int sf_test_wire_parse_stats(uint64_t out[4]) {
-  if (!out) return SF_EINVAL;
-  for (int k = 0; k < 4; k++) out[k] = g_parse_stats[k].load(std::memory_order_relaxed);
-  return SF_OK;
-}
+int sf_test_wire_parse_stats(uint64_t out[4]) { return g_parse_stats.read(out); }
 
 }  // extern "C"

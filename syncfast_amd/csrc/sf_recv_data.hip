@@ -156,11 +156,7 @@ __global__ void __launch_bounds__(256) data_compare_kernel(const uint32_t* __res
   if (!same) atomicAdd(bad, 1ull);
 }
 
-std::atomic<uint64_t> g_data_stats[4];  // sf_test_block_data_stats
-
-inline void reset_stats() {
-  for (auto& v : g_data_stats) v.store(0, std::memory_order_relaxed);
-}
+sfi::Stats4 g_data_stats;  // sf_test_block_data_stats
 
 }  // namespace
 
@@ -184,22 +180,22 @@ struct Parsed {
   int stop = sfwp::kEnd;
 };
 
-inline dim3 grid_for(uint64_t n) { return dim3((unsigned)ceil_div(n, 256)); }
-
 // Hash the first `count` payloads where they lie and compare; *bad = the
 // mismatches.  Blocking.
 int verify(const uint8_t* d_wire, uint64_t n, const Outputs& o, uint64_t count, uint64_t* bad, hipStream_t s) {
   Scratch comp(s);  // the mismatch counter, then the computed digests
-  int rc = stream_alloc(&comp.p, 256 + count * 20, s);
+  ScratchLayout L;
+  const size_t bad_at = L.add(8);
+  int rc = stream_alloc(&comp.p, L.total() + count * 20, s);
   if (rc != SF_OK) return rc;
-  unsigned long long* d_bad = static_cast<unsigned long long*>(comp.p);
-  void* computed = static_cast<uint8_t*>(comp.p) + 256;
+  unsigned long long* d_bad = L.at<unsigned long long>(comp.p, bad_at);
+  uint32_t* computed = L.at<uint32_t>(comp.p, L.total());
   SF_HIP(hipMemsetAsync(d_bad, 0, sizeof(*d_bad), s));
-  if ((rc = launch_table(d_wire, n, o.d_offsets, o.d_sizes, count, computed, nullptr, s)) != SF_OK) return rc;
-  clear_stale_error();
-  hipLaunchKernelGGL(data_compare_kernel, grid_for(count), dim3(256), 0, s, static_cast<const uint32_t*>(o.d_digests),
-                     static_cast<const uint32_t*>(computed), o.d_sizes, count, o.d_ok, d_bad);
-  SF_HIP(hipGetLastError());
+  rc = launch_table(d_wire, n, o.d_offsets, o.d_sizes, count, computed, nullptr, s);
+  if (rc == SF_OK)
+    rc = launch(data_compare_kernel, grid256(count), dim3(256), s, static_cast<const uint32_t*>(o.d_digests), computed,
+                o.d_sizes, count, o.d_ok, d_bad);
+  if (rc != SF_OK) return rc;
   unsigned long long h = 0;
   SF_HIP(hipMemcpyAsync(&h, d_bad, sizeof(h), hipMemcpyDeviceToHost, s));
   SF_HIP(hipStreamSynchronize(s));
@@ -234,7 +230,7 @@ int parse_on_host(const uint8_t* h_wire, uint64_t n, const Provide& provide, Out
   bool too_large = false;
   sfwp::parse_data_run(h_wire, n, nullptr, nullptr, nullptr, 0, &out->count, &out->consumed, &out->stop, &out->need,
                        &too_large);  // the count first: it sizes the outputs
-  g_data_stats[1].store(out->count, std::memory_order_relaxed);
+  g_data_stats.set(1, out->count);
   if (too_large) return SF_ERANGE;
   int rc = provide(out->count, o);
   if (rc != SF_OK) return rc;
@@ -282,7 +278,7 @@ int find_messages(const uint8_t* d_wire, const uint8_t* h_wire, uint64_t n, cons
   uint64_t total = 0;
   SF_HIP(hipMemcpyAsync(&total, sc.ends + sc.nw - 1, 8, hipMemcpyDeviceToHost, s));
   SF_HIP(hipStreamSynchronize(s));
-  g_data_stats[0].store(total, std::memory_order_relaxed);
+  g_data_stats.set(0, total);
   if (total > n / sfwp::kTag + 1) return SF_EIO;  // cannot be: two candidates' tags do not overlap
 
   uint64_t count = 0;
@@ -292,13 +288,10 @@ int find_messages(const uint8_t* d_wire, const uint8_t* h_wire, uint64_t n, cons
     if ((rc = stream_alloc(&list.p, total * 16, s)) != SF_OK) return rc;
     uint64_t* pos = static_cast<uint64_t*>(list.p);
     uint64_t* len = pos + total;
-    clear_stale_error();
-    hipLaunchKernelGGL(data_compact_kernel, grid_for(sc.nw), dim3(256), 0, s, d_wire, n, sc.words, sc.ends, sc.nw, total,
-                       pos, len);
-    SF_HIP(hipGetLastError());
-    clear_stale_error();
-    hipLaunchKernelGGL(data_link_kernel, grid_for(total), dim3(256), 0, s, pos, len, total, res);
-    SF_HIP(hipGetLastError());
+    rc = launch(data_compact_kernel, grid256(sc.nw), dim3(256), s, d_wire, n, sc.words, sc.ends, sc.nw, total, pos,
+                len);
+    if (rc == SF_OK) rc = launch(data_link_kernel, grid256(total), dim3(256), s, pos, len, total, res);
+    if (rc != SF_OK) return rc;
     struct {
       unsigned long long first_bad;
       uint64_t pos0;
@@ -326,8 +319,8 @@ int find_messages(const uint8_t* d_wire, const uint8_t* h_wire, uint64_t n, cons
       SF_HIP(hipStreamSynchronize(s));
       const uint64_t* hp = static_cast<const uint64_t*>(plist);
       count = sfwp::walk_candidates(hp, hp + total, total, static_cast<uint64_t*>(pchain));
-      g_data_stats[2].store(1, std::memory_order_relaxed);
-      g_data_stats[3].store(total * 16, std::memory_order_relaxed);
+      g_data_stats.set(2, 1);
+      g_data_stats.set(3, total * 16);
       if (count) {
         if ((rc = stream_alloc(&idx.p, count * 8, s)) != SF_OK) return rc;
         SF_HIP(hipMemcpyAsync(idx.p, pchain, count * 8, hipMemcpyHostToDevice, s));
@@ -337,10 +330,9 @@ int find_messages(const uint8_t* d_wire, const uint8_t* h_wire, uint64_t n, cons
     }
     if ((rc = provide(count, o)) != SF_OK) return rc;
     if (count) {
-      clear_stale_error();
-      hipLaunchKernelGGL(data_extract_kernel, grid_for(count), dim3(256), 0, s, d_wire, n, pos, len, chain, count,
-                         static_cast<uint32_t*>(o->d_digests), o->d_sizes, o->d_offsets, o->cap, res);
-      SF_HIP(hipGetLastError());
+      rc = launch(data_extract_kernel, grid256(count), dim3(256), s, d_wire, n, pos, len, chain, count,
+                  static_cast<uint32_t*>(o->d_digests), o->d_sizes, o->d_offsets, o->cap, res);
+      if (rc != SF_OK) return rc;
       SF_HIP(hipMemcpyAsync(&r, res, sizeof(Result), hipMemcpyDeviceToHost, s));
       SF_HIP(hipStreamSynchronize(s));
       if (r.too_large) return SF_ERANGE;
@@ -348,7 +340,7 @@ int find_messages(const uint8_t* d_wire, const uint8_t* h_wire, uint64_t n, cons
   } else if ((rc = provide(0, o)) != SF_OK) {
     return rc;
   }
-  g_data_stats[1].store(count, std::memory_order_relaxed);
+  g_data_stats.set(1, count);
   out->count = count;
   out->consumed = count ? r.end : 0;
   // what stands at E: after a message the extract kernel brought its bytes
@@ -374,7 +366,7 @@ struct Results {
 };
 
 int check_args(const Results& r, const void* wire, uint64_t n_bytes) {
-  reset_stats();
+  g_data_stats.reset();
   if (r.n_out) *r.n_out = 0;
   if (r.consumed) *r.consumed = 0;
   if (r.stop) *r.stop = SF_WIRE_END;
@@ -485,10 +477,6 @@ int sf_receive_block_data_buffer(const void* wire, uint64_t n_bytes, sf_block_si
   });
 }
 
-int sf_test_block_data_stats(uint64_t out[4]) {
-  if (!out) return SF_EINVAL;
-  for (int k = 0; k < 4; k++) out[k] = g_data_stats[k].load(std::memory_order_relaxed);
-  return SF_OK;
-}
+int sf_test_block_data_stats(uint64_t out[4]) { return g_data_stats.read(out); }
 
 }  // extern "C"

@@ -84,20 +84,6 @@ struct FilesRules {
   }
 };
 
-// The 64 bitmap bits from position q on (bits past the bitmap are 0).
-__device__ __forceinline__ unsigned long long bits_from(const unsigned long long* __restrict__ words, uint64_t nw,
-                                                        uint64_t q) {
-  const uint64_t w = q >> 6;
-  const uint32_t s = (uint32_t)(q & 63);
-  unsigned long long v = w < nw ? words[w] >> s : 0ull;
-  if (s && w + 1 < nw) v |= words[w + 1] << (64 - s);
-  return v;
-}
-
-__device__ __forceinline__ unsigned long long low_bits(uint32_t k) {  // k in 0..64
-  return k >= 64 ? ~0ull : (1ull << k) - 1;
-}
-
 constexpr unsigned long long kOneFile = 1ull << 32, kOneBlock = 1ull;
 
 __global__ void __launch_bounds__(256) files_chain_kernel(const uint8_t* __restrict__ data, uint64_t n,
@@ -232,11 +218,7 @@ __global__ void __launch_bounds__(256) files_offsets_kernel(const uint64_t* __re
   if (t == nf) first[nf] = nb;
 }
 
-struct Widen {
-  __host__ __device__ uint64_t operator()(uint32_t v) const { return (uint64_t)v; }
-};
-
-std::atomic<uint64_t> g_files_stats[4];  // sf_test_recv_files_stats
+sfi::Stats4 g_files_stats;  // sf_test_recv_files_stats
 
 }  // namespace
 
@@ -279,8 +261,8 @@ int files_on_host(const FilesArgs& a, const uint8_t* d_wire, uint64_t n, uint64_
   const sfwp::FilesOut o{dig.data(), sizes.data(), offs.data(), bfile.data(), r.n_blocks, nat.data(),
                          nlen.data(), first.data(), fsize.data(), r.n_files};
   sfwp::parse_files_run(wire.data(), n, a.open != 0, a.base_offset, o, &r);
-  g_files_stats[1].store(r.messages, std::memory_order_relaxed);
-  g_files_stats[2].store(1, std::memory_order_relaxed);
+  g_files_stats.set(1, r.messages);
+  g_files_stats.set(2, 1);
   *a.n_blocks = r.n_blocks;
   *a.n_files = r.n_files;
   *a.consumed = r.consumed;
@@ -327,42 +309,30 @@ int files_device(const FilesArgs& a, const uint8_t* d_wire, uint64_t n, hipStrea
   Result* res = static_cast<Result*>(sc.result);
   // the kinds' counts per word and their scan
   size_t tmp = 0;
-  {
-    unsigned long long* in = nullptr;
-    if (rocprim::inclusive_scan(nullptr, tmp, in, in, (size_t)sc.nw, rocprim::plus<unsigned long long>(), s) !=
-        hipSuccess) {
-      (void)hipGetLastError();
-      return SF_ENODEV;
-    }
-  }
-  const size_t wb = align256(sc.nw * 8);
+  unsigned long long* const nul = nullptr;
+  if ((rc = scan_inclusive(nullptr, tmp, nul, nul, sc.nw, s)) != SF_OK) return rc;
+  ScratchLayout KL;
+  const size_t kinds_at = KL.add(sc.nw * 8), kends_at = KL.add(sc.nw * 8);
   Scratch ks(s);
-  if ((rc = stream_alloc(&ks.p, 2 * wb + tmp + 8, s)) != SF_OK) return rc;
-  unsigned long long* kinds = static_cast<unsigned long long*>(ks.p);
-  unsigned long long* kends = reinterpret_cast<unsigned long long*>(static_cast<uint8_t*>(ks.p) + wb);
-  void* scan_tmp = static_cast<uint8_t*>(ks.p) + 2 * wb;
-  const dim3 gw((unsigned)ceil_div(sc.nw, 256));
-  clear_stale_error();
-  hipLaunchKernelGGL(files_chain_kernel, gw, dim3(256), 0, s, d_wire, n, sc.words, sc.ends, sc.nw, a.open, kinds, res);
-  SF_HIP(hipGetLastError());
-  if (rocprim::inclusive_scan(scan_tmp, tmp, kinds, kends, (size_t)sc.nw, rocprim::plus<unsigned long long>(), s) !=
-      hipSuccess) {
-    (void)hipGetLastError();
-    return SF_ENODEV;
-  }
+  if ((rc = stream_alloc(&ks.p, KL.total() + tmp + 8, s)) != SF_OK) return rc;
+  unsigned long long* kinds = KL.at<unsigned long long>(ks.p, kinds_at);
+  unsigned long long* kends = KL.at<unsigned long long>(ks.p, kends_at);
+  const dim3 gw = grid256(sc.nw);
+  rc = launch(files_chain_kernel, gw, dim3(256), s, d_wire, n, sc.words, sc.ends, sc.nw, a.open, kinds, res);
+  if (rc == SF_OK) rc = scan_inclusive(KL.at<void>(ks.p, KL.total()), tmp, kinds, kends, sc.nw, s);
+  if (rc != SF_OK) return rc;
   const FilesOutputs o{static_cast<uint32_t*>(a.d_digests), a.d_sizes, a.d_block_file, block_cap, a.d_name_at,
                        a.d_name_len, a.d_first, file_cap};
-  clear_stale_error();
-  hipLaunchKernelGGL(files_extract_kernel, gw, dim3(256), 0, s, d_wire, n, sc.words, sc.ends, kinds, kends, sc.nw,
-                     a.open, o, res);
-  SF_HIP(hipGetLastError());
+  rc = launch(files_extract_kernel, gw, dim3(256), s, d_wire, n, sc.words, sc.ends, kinds, kends, sc.nw, a.open, o,
+              res);
+  if (rc != SF_OK) return rc;
   Result h{};
   SF_HIP(hipMemcpyAsync(&h, res, sizeof(Result), hipMemcpyDeviceToHost, s));
   SF_HIP(hipStreamSynchronize(s));
-  g_files_stats[0].store(h.cand, std::memory_order_relaxed);
+  g_files_stats.set(0, h.cand);
   if (h.msgs && !(h.first_bad & 1ull))  // a candidate inside the last chained message
     return files_on_host(a, d_wire, n, block_cap, file_cap, query, s);
-  g_files_stats[1].store(h.msgs, std::memory_order_relaxed);
+  g_files_stats.set(1, h.msgs);
   const uint64_t nb = h.blocks, nf = h.files;
   *a.n_blocks = nb;
   *a.n_files = nf;
@@ -382,25 +352,16 @@ int files_device(const FilesArgs& a, const uint8_t* d_wire, uint64_t n, hipStrea
   if (nb) {
     auto in = rocprim::make_transform_iterator(a.d_sizes, Widen());
     size_t gtmp = 0;
-    if (rocprim::exclusive_scan(nullptr, gtmp, in, G, (uint64_t)0, (size_t)nb, rocprim::plus<uint64_t>(), s) !=
-        hipSuccess) {
-      (void)hipGetLastError();
-      return SF_ENODEV;
-    }
-    const size_t gb = align256(nb * 8);
-    if ((rc = stream_alloc(&gs.p, gb + gtmp + 8, s)) != SF_OK) return rc;
-    G = static_cast<uint64_t*>(gs.p);
-    if (rocprim::exclusive_scan(static_cast<uint8_t*>(gs.p) + gb, gtmp, in, G, (uint64_t)0, (size_t)nb,
-                                rocprim::plus<uint64_t>(), s) != hipSuccess) {
-      (void)hipGetLastError();
-      return SF_ENODEV;
-    }
+    if ((rc = scan_exclusive(nullptr, gtmp, in, G, 0, nb, s)) != SF_OK) return rc;
+    ScratchLayout GL;
+    const size_t g_at = GL.add(nb * 8);
+    if ((rc = stream_alloc(&gs.p, GL.total() + gtmp + 8, s)) != SF_OK) return rc;
+    G = GL.at<uint64_t>(gs.p, g_at);
+    if ((rc = scan_exclusive(GL.at<void>(gs.p, GL.total()), gtmp, in, G, 0, nb, s)) != SF_OK) return rc;
   }
-  clear_stale_error();
-  hipLaunchKernelGGL(files_offsets_kernel, dim3((unsigned)ceil_div(std::max(nb, nf + 1), 256)), dim3(256), 0, s, G,
-                     a.d_sizes, a.d_block_file, nb, a.d_first, nf, a.open, a.base_offset, a.d_offsets, a.d_file_size,
-                     &res->end_offset);
-  SF_HIP(hipGetLastError());
+  rc = launch(files_offsets_kernel, grid256(std::max(nb, nf + 1)), dim3(256), s, G, a.d_sizes, a.d_block_file, nb,
+              a.d_first, nf, a.open, a.base_offset, a.d_offsets, a.d_file_size, &res->end_offset);
+  if (rc != SF_OK) return rc;
   if (a.set && nb && (rc = sf_block_set_lookup(a.set, a.d_digests, nb, a.d_rows, s)) != SF_OK) return rc;
   unsigned long long end_offset = a.base_offset;
   if (nf) SF_HIP(hipMemcpyAsync(&end_offset, &res->end_offset, 8, hipMemcpyDeviceToHost, s));
@@ -410,7 +371,7 @@ int files_device(const FilesArgs& a, const uint8_t* d_wire, uint64_t n, hipStrea
 }
 
 int receive_files(const FilesArgs& a, const void* d_wire, uint64_t n_bytes, hipStream_t s) {
-  for (auto& v : g_files_stats) v.store(0, std::memory_order_relaxed);
+  g_files_stats.reset();
   const uint64_t carried = a.open ? 1 : 0;
   if (a.n_blocks) *a.n_blocks = 0;
   if (a.n_files) *a.n_files = carried;
@@ -448,10 +409,6 @@ int sf_receive_files_device(const sf_block_set* set, const void* d_wire, uint64_
   });
 }
 
-int sf_test_recv_files_stats(uint64_t out[4]) {
-  if (!out) return SF_EINVAL;
-  for (int k = 0; k < 4; k++) out[k] = g_files_stats[k].load(std::memory_order_relaxed);
-  return SF_OK;
-}
+int sf_test_recv_files_stats(uint64_t out[4]) { return g_files_stats.read(out); }
 
 }  // extern "C"

@@ -1,10 +1,12 @@
-// sf_recv_scan.hpp -- what the two receive parsers share (sf_recv.hip for
-// FILE_BLOCK runs, sf_recv_data.hip for BLOCK_DATA runs; each stays its own
-// translation unit with its own code objects): the first two steps of a
-// parse and the upload of a run that lies in host memory.
+// sf_recv_scan.hpp -- what the three receive parsers share (sf_recv.hip for
+// FILE_BLOCK runs, sf_recv_data.hip for BLOCK_DATA runs, sf_recv_files.hip
+// for a whole GetFiles stream; each stays its own translation unit with its
+// own code objects): the first two steps of a parse, the bitmap reads of the
+// chain kernels, the 32-to-64-bit widening of the size scans, and the upload
+// of a run that lies in host memory.
 //
 // A message start cannot be told from digest or payload bytes that happen to
-// hold the same bytes, so both parsers first find every position where a
+// hold the same bytes, so every parser first finds every position where a
 // message could start and then decide, each in its own way, which of them
 // chain from byte 0:
 //
@@ -38,9 +40,7 @@
 #include <stdint.h>
 #include <string.h>
 
-#include <rocprim/device/device_scan.hpp>
-
-#include "sf_internal.hpp"
+#include "sf_device.hpp"
 #include "sf_stage.hpp"
 
 namespace sfrs {
@@ -131,6 +131,26 @@ __device__ __forceinline__ void store_digest(uint32_t* o, const uint8_t* d) {
            (uint32_t)d[4 * j + 3] << 24;
 }
 
+// The 64 bitmap bits from position q on (bits past the bitmap are 0).
+__device__ __forceinline__ unsigned long long bits_from(const unsigned long long* __restrict__ words, uint64_t nw,
+                                                        uint64_t q) {
+  const uint64_t w = q >> 6;
+  const uint32_t s = (uint32_t)(q & 63);
+  unsigned long long v = w < nw ? words[w] >> s : 0ull;
+  if (s && w + 1 < nw) v |= words[w + 1] << (64 - s);
+  return v;
+}
+
+__device__ __forceinline__ unsigned long long low_bits(uint32_t k) {  // k in 0..64
+  return k >= 64 ? ~0ull : (1ull << k) - 1;
+}
+
+// The parsed sizes are 32 bits wide and their running offsets 64: the scans
+// over them read through a transform iterator of this.
+struct Widen {
+  __host__ __device__ uint64_t operator()(uint32_t v) const { return (uint64_t)v; }
+};
+
 // What scan_candidates leaves in stream-ordered scratch, which goes back
 // when this goes out of scope.
 struct Scan {
@@ -151,36 +171,23 @@ int scan_candidates(const uint8_t* d_wire, uint64_t n, hipStream_t s, Scan* out)
   using namespace sfi;
   const uint64_t nw = ceil_div(n, 64);
   size_t tmp = 0;
-  {
-    uint32_t* in = nullptr;
-    uint64_t* o = nullptr;
-    if (rocprim::inclusive_scan(nullptr, tmp, in, o, (size_t)nw, rocprim::plus<uint64_t>(), s) != hipSuccess) {
-      (void)hipGetLastError();
-      return SF_ENODEV;
-    }
-  }
-  const size_t wb = align256(nw * 8), cb = align256(nw * 4);
-  const int rc = stream_alloc(&out->ws.p, 256 + 2 * wb + cb + tmp + 8, s);
+  int rc = scan_inclusive(nullptr, tmp, static_cast<uint32_t*>(nullptr), static_cast<uint64_t*>(nullptr), nw, s);
   if (rc != SF_OK) return rc;
-  uint8_t* base = static_cast<uint8_t*>(out->ws.p);
+  ScratchLayout L;
+  const size_t result_at = L.add(256), words_at = L.add(nw * 8), ends_at = L.add(nw * 8), counts_at = L.add(nw * 4);
+  if ((rc = stream_alloc(&out->ws.p, L.total() + tmp + 8, s)) != SF_OK) return rc;
+  void* base = out->ws.p;
   out->nw = nw;
-  out->result = base;
-  out->words = reinterpret_cast<unsigned long long*>(base + 256);
-  out->ends = reinterpret_cast<uint64_t*>(base + 256 + wb);
-  out->counts = reinterpret_cast<uint32_t*>(base + 256 + 2 * wb);
-  void* scan_tmp = base + 256 + 2 * wb + cb;
+  out->result = L.at<void>(base, result_at);
+  out->words = L.at<unsigned long long>(base, words_at);
+  out->ends = L.at<uint64_t>(base, ends_at);
+  out->counts = L.at<uint32_t>(base, counts_at);
   SF_HIP(hipMemsetAsync(out->result, 0, 256, s));
   SF_HIP(hipMemsetAsync(out->result, 0xFF, 8, s));
-  clear_stale_error();
-  hipLaunchKernelGGL(candidates_kernel<Rules>, dim3((unsigned)ceil_div(n, 256 * kPerLane)), dim3(256), 0, s, d_wire, n,
-                     out->words, out->counts);
-  SF_HIP(hipGetLastError());
-  if (rocprim::inclusive_scan(scan_tmp, tmp, out->counts, out->ends, (size_t)nw, rocprim::plus<uint64_t>(), s) !=
-      hipSuccess) {
-    (void)hipGetLastError();
-    return SF_ENODEV;
-  }
-  return SF_OK;
+  rc = launch(candidates_kernel<Rules>, dim3((unsigned)ceil_div(n, 256 * kPerLane)), dim3(256), s, d_wire, n,
+              out->words, out->counts);
+  if (rc != SF_OK) return rc;
+  return scan_inclusive(L.at<void>(base, L.total()), tmp, out->counts, out->ends, nw, s);
 }
 
 // The run wire[0, n_bytes) (n_bytes > 0) to HBM through the lease's two

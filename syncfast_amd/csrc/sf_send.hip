@@ -34,10 +34,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <rocprim/device/device_scan.hpp>
-
 #include "sf_copy_plan.hpp"
-#include "sf_internal.hpp"
+#include "sf_device.hpp"
 #include "sf_wire_data.hpp"
 
 namespace {
@@ -124,26 +122,50 @@ using namespace sfi;
 
 namespace {
 
-// kernel<<<pieces of at most kSendMaxPerLaunch lanes>>>(args(first, count)...)
-template <typename Launch>
-int in_pieces(uint64_t n, Launch&& launch) {
-  for (uint64_t first = 0; first < n; first += kSendMaxPerLaunch) {
-    const uint64_t cnt = std::min(kSendMaxPerLaunch, n - first);
-    clear_stale_error();
-    launch(first, cnt, dim3((unsigned)ceil_div(cnt, 256)));
-    SF_HIP(hipGetLastError());
+void wire_run_discard(sf_wire_run* run, hipStream_t s) {
+  stream_free(run->bytes, s);
+  if (run->done) (void)hipEventDestroy(run->done);
+  delete run;
+}
+
+}  // namespace
+
+sf_wire_run* sfi::wire_run_empty() { return new sf_wire_run{nullptr, 0, 0, -1, nullptr}; }
+
+int sfi::wire_run_begin(uint64_t n_bytes, uint64_t n_messages, hipStream_t s, sf_wire_run** out) {
+  *out = nullptr;
+  int dev = 0;
+  SF_HIP(hipGetDevice(&dev));
+  sf_wire_run* run = new sf_wire_run{nullptr, n_bytes, n_messages, dev, nullptr};
+  int rc = stream_alloc(reinterpret_cast<void**>(&run->bytes), n_bytes, s);
+  if (rc == SF_OK) rc = hip_err(hipEventCreateWithFlags(&run->done, hipEventDisableTiming));
+  if (rc != SF_OK) {
+    wire_run_discard(run, s);
+    return rc;
   }
+  *out = run;
   return SF_OK;
 }
 
-sf_wire_run* empty_run() { return new sf_wire_run{nullptr, 0, 0, -1, nullptr}; }
+int sfi::wire_run_finish(sf_wire_run* run, int rc, hipStream_t s, sf_wire_run** out) {
+  if (!run) return rc;
+  if (rc == SF_OK) rc = hip_err(hipEventRecord(run->done, s));
+  if (rc != SF_OK) {
+    wire_run_discard(run, s);
+    return rc;
+  }
+  *out = run;
+  return SF_OK;
+}
+
+namespace {
 
 int build_run(const uint8_t* d_src, uint64_t src_len, const uint8_t* d_digests, const uint64_t* d_src_off,
               const uint32_t* d_sizes, uint64_t n, sf_wire_run** out, hipStream_t s) {
   if (!out) return SF_EINVAL;
   *out = nullptr;
   if (n == 0) {
-    *out = empty_run();
+    *out = wire_run_empty();
     return SF_OK;
   }
   if (!d_src || !d_digests || !d_src_off || !d_sizes || n > kMaxJobs) return SF_EINVAL;
@@ -153,62 +175,44 @@ int build_run(const uint8_t* d_src, uint64_t src_len, const uint8_t* d_digests, 
   uint64_t bound = 0;
   if (__builtin_mul_overflow(n, 44 + std::min<uint64_t>(src_len, 0xFFFFFFFFull), &bound)) return SF_ENOMEM;
 
-  int dev = 0;
-  SF_HIP(hipGetDevice(&dev));
   size_t tmp = 0;
-  {
-    uint64_t* nul = nullptr;
-    if (rocprim::inclusive_scan(nullptr, tmp, nul, nul, (size_t)n, rocprim::plus<uint64_t>(), s) != hipSuccess) {
-      (void)hipGetLastError();
-      return SF_ENODEV;
-    }
-  }
+  uint64_t* const nul = nullptr;
+  int rc = scan_inclusive(nullptr, tmp, nul, nul, n, s);
+  if (rc != SF_OK) return rc;
   // ends[0, n) and the flag behind them (read back together), lens, then the
   // payloads' offsets in the run, then the scan's
-  const size_t eb = align256((n + 1) * 8), lb = align256(n * 8);
+  ScratchLayout L;
+  const size_t ends_at = L.add((n + 1) * 8), lens_at = L.add(n * 8), dst_at = L.add(n * 8);
   Scratch ws(s);
-  int rc = stream_alloc(&ws.p, eb + 2 * lb + tmp + 8, s);
+  rc = stream_alloc(&ws.p, L.total() + tmp + 8, s);
   if (rc != SF_OK) return rc;
-  uint8_t* w = static_cast<uint8_t*>(ws.p);
-  uint64_t* ends = reinterpret_cast<uint64_t*>(w);
-  uint64_t* lens = reinterpret_cast<uint64_t*>(w + eb);
-  uint64_t* dst_off = reinterpret_cast<uint64_t*>(w + eb + lb);
-  void* scan_tmp = w + eb + 2 * lb;
+  uint64_t* ends = L.at<uint64_t>(ws.p, ends_at);
+  uint64_t* lens = L.at<uint64_t>(ws.p, lens_at);
+  uint64_t* dst_off = L.at<uint64_t>(ws.p, dst_at);
+  void* scan_tmp = L.at<void>(ws.p, L.total());
   unsigned long long* flag = reinterpret_cast<unsigned long long*>(ends + n);
   SF_HIP(hipMemsetAsync(flag, 0, 8, s));
-  rc = in_pieces(n, [&](uint64_t first, uint64_t cnt, dim3 grid) {
-    hipLaunchKernelGGL(send_plan_kernel, grid, dim3(256), 0, s, d_src_off + first, d_sizes + first, cnt, src_len,
-                       lens + first, flag);
+  rc = for_pieces(n, kSendMaxPerLaunch, [&](uint64_t first, uint64_t cnt) {
+    return launch(send_plan_kernel, grid256(cnt), dim3(256), s, d_src_off + first, d_sizes + first, cnt, src_len,
+                  lens + first, flag);
   });
+  if (rc == SF_OK) rc = scan_inclusive(scan_tmp, tmp, lens, ends, n, s);
   if (rc != SF_OK) return rc;
-  if (rocprim::inclusive_scan(scan_tmp, tmp, lens, ends, (size_t)n, rocprim::plus<uint64_t>(), s) != hipSuccess) {
-    (void)hipGetLastError();
-    return SF_ENODEV;
-  }
   uint64_t back[2] = {0, 0};  // the run's length, the flag
   SF_HIP(hipMemcpyAsync(back, ends + n - 1, 16, hipMemcpyDeviceToHost, s));
   SF_HIP(hipStreamSynchronize(s));
   if (back[1]) return SF_ERANGE;
   const uint64_t total = back[0];
 
-  sf_wire_run* run = new sf_wire_run{nullptr, total, n, dev, nullptr};
-  rc = stream_alloc(reinterpret_cast<void**>(&run->bytes), total, s);
-  if (rc == SF_OK) rc = hip_err(hipEventCreateWithFlags(&run->done, hipEventDisableTiming));
+  sf_wire_run* run = nullptr;
+  rc = wire_run_begin(total, n, s, &run);
   if (rc == SF_OK)
-    rc = in_pieces(n, [&](uint64_t first, uint64_t cnt, dim3 grid) {
-      hipLaunchKernelGGL(send_headers_kernel, grid, dim3(256), 0, s, d_digests + first * 20, d_sizes + first,
-                         ends + first, cnt, run->bytes, dst_off + first);
+    rc = for_pieces(n, kSendMaxPerLaunch, [&](uint64_t first, uint64_t cnt) {
+      return launch(send_headers_kernel, grid256(cnt), dim3(256), s, d_digests + first * 20, d_sizes + first,
+                    ends + first, cnt, run->bytes, dst_off + first);
     });
   if (rc == SF_OK) rc = copy_blocks(d_src, src_len, run->bytes, total, d_src_off, dst_off, d_sizes, nullptr, n, nullptr, s);
-  if (rc == SF_OK) rc = hip_err(hipEventRecord(run->done, s));
-  if (rc != SF_OK) {
-    stream_free(run->bytes, s);
-    if (run->done) (void)hipEventDestroy(run->done);
-    delete run;
-    return rc;
-  }
-  *out = run;
-  return SF_OK;
+  return wire_run_finish(run, rc, s, out);
 }
 
 int serve(const sf_block_set* set, const uint64_t* d_row_off, const uint32_t* d_row_size, const uint8_t* d_src,
@@ -221,25 +225,26 @@ int serve(const sf_block_set* set, const uint64_t* d_row_off, const uint32_t* d_
   *stop = SF_WIRE_END;
   if (n_bytes > kMaxRequestBytes || (n_bytes && (!d_req || !set))) return SF_EINVAL;
   if (n_bytes == 0) {
-    *out = empty_run();
+    *out = wire_run_empty();
     return SF_OK;
   }
   const uint64_t slots = n_bytes / sfwp::kGetBlock;
   // first[0]: the first slot that is no message; first[1]: the first request
   // without a row (UINT64_MAX: none).  Then the digests, rows and jobs.
-  const size_t db = align256(slots * 20), rb = align256(slots * 8), sb = align256(slots * 4);
+  ScratchLayout L;
+  const size_t first_at = L.add(16), table_at = L.add(slots * 20), rows_at = L.add(slots * 8),
+               src_at = L.add(slots * 8), sizes_at = L.add(slots * 4);
   Scratch ws(s);
-  int rc = stream_alloc(&ws.p, 256 + db + 2 * rb + sb, s);
+  int rc = stream_alloc(&ws.p, L.total(), s);
   if (rc != SF_OK) return rc;
-  uint8_t* w = static_cast<uint8_t*>(ws.p);
-  unsigned long long* first = reinterpret_cast<unsigned long long*>(w);
-  uint32_t* table = reinterpret_cast<uint32_t*>(w + 256);
-  int64_t* rows = reinterpret_cast<int64_t*>(w + 256 + db);
-  uint64_t* src_off = reinterpret_cast<uint64_t*>(w + 256 + db + rb);
-  uint32_t* sizes = reinterpret_cast<uint32_t*>(w + 256 + db + 2 * rb);
+  unsigned long long* first = L.at<unsigned long long>(ws.p, first_at);
+  uint32_t* table = L.at<uint32_t>(ws.p, table_at);
+  int64_t* rows = L.at<int64_t>(ws.p, rows_at);
+  uint64_t* src_off = L.at<uint64_t>(ws.p, src_at);
+  uint32_t* sizes = L.at<uint32_t>(ws.p, sizes_at);
   SF_HIP(hipMemsetAsync(first, 0xFF, 16, s));
-  rc = in_pieces(slots, [&](uint64_t f, uint64_t cnt, dim3 grid) {
-    hipLaunchKernelGGL(send_slots_kernel, grid, dim3(256), 0, s, d_req, f, cnt, first);
+  rc = for_pieces(slots, kSendMaxPerLaunch, [&](uint64_t f, uint64_t cnt) {
+    return launch(send_slots_kernel, grid256(cnt), dim3(256), s, d_req, f, cnt, first);
   });
   if (rc != SF_OK) return rc;
   uint64_t fail = 0;
@@ -254,14 +259,14 @@ int serve(const sf_block_set* set, const uint64_t* d_row_off, const uint32_t* d_
   uint64_t missing = UINT64_MAX;
   if (count) {
     if (!d_row_off || !d_row_size) return SF_EINVAL;
-    rc = in_pieces(count, [&](uint64_t f, uint64_t cnt, dim3 grid) {
-      hipLaunchKernelGGL(send_digests_kernel, grid, dim3(256), 0, s, d_req, f, cnt, table);
+    rc = for_pieces(count, kSendMaxPerLaunch, [&](uint64_t f, uint64_t cnt) {
+      return launch(send_digests_kernel, grid256(cnt), dim3(256), s, d_req, f, cnt, table);
     });
     if (rc == SF_OK) rc = sf_block_set_lookup(set, table, count, rows, s);
     if (rc == SF_OK)
-      rc = in_pieces(count, [&](uint64_t f, uint64_t cnt, dim3 grid) {
-        hipLaunchKernelGGL(send_jobs_kernel, grid, dim3(256), 0, s, rows, d_row_off, d_row_size, f, cnt, src_off,
-                           sizes, first + 1);
+      rc = for_pieces(count, kSendMaxPerLaunch, [&](uint64_t f, uint64_t cnt) {
+        return launch(send_jobs_kernel, grid256(cnt), dim3(256), s, rows, d_row_off, d_row_size, f, cnt, src_off, sizes,
+                      first + 1);
       });
     if (rc != SF_OK) return rc;
     SF_HIP(hipMemcpyAsync(&missing, first + 1, 8, hipMemcpyDeviceToHost, s));

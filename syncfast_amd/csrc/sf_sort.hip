@@ -11,7 +11,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "sf_internal.hpp"
+#include "sf_device.hpp"
 #include "sha1_device.hpp"
 #include "../../include/syncfast_amd_test.h"
 
@@ -191,15 +191,16 @@ size_t class_order_workspace(uint64_t n, uint32_t kmax) {
 }
 
 template <uint32_t BINS>
-static void class_order_launch(const uint32_t* d_sizes, uint64_t n, uint32_t mbits, uint32_t kmax, uint32_t* hist,
+static int class_order_launch(const uint32_t* d_sizes, uint64_t n, uint32_t mbits, uint32_t kmax, uint32_t* hist,
                                uint32_t ntiles, uint32_t* d_order, hipStream_t s) {
   uint32_t* totals = hist + (uint64_t)ntiles * BINS;
-  sfi::clear_stale_error();
-  hipLaunchKernelGGL(sf::class_hist_kernel<BINS>, dim3(ntiles), dim3(sf::kSortThreads), 0, s, d_sizes, n, mbits, kmax,
-                     hist, ntiles);
-  hipLaunchKernelGGL(sf::class_scan_kernel, dim3(BINS), dim3(sf::kSortThreads), 0, s, hist, ntiles, totals);
-  hipLaunchKernelGGL(sf::class_scatter_kernel<BINS>, dim3(ntiles), dim3(sf::kSortThreads), 0, s, d_sizes, n, mbits,
-                     kmax, hist, totals, ntiles, d_order);
+  const dim3 block(sf::kSortThreads);
+  int rc = launch(sf::class_hist_kernel<BINS>, dim3(ntiles), block, s, d_sizes, n, mbits, kmax, hist, ntiles);
+  if (rc == SF_OK) rc = launch(sf::class_scan_kernel, dim3(BINS), block, s, hist, ntiles, totals);
+  if (rc == SF_OK)
+    rc = launch(sf::class_scatter_kernel<BINS>, dim3(ntiles), block, s, d_sizes, n, mbits, kmax, hist, totals, ntiles,
+                d_order);
+  return rc;
 }
 
 int class_order(const uint32_t* d_sizes, uint64_t n, uint32_t mbits, uint32_t kmax, void* d_ws, uint32_t* d_order,
@@ -208,13 +209,9 @@ int class_order(const uint32_t* d_sizes, uint64_t n, uint32_t mbits, uint32_t km
   if (n > 0xFFFFFFFFull || kmax >= sf::kSortBinsMax) return SF_EINVAL;
   const uint32_t ntiles = (uint32_t)((n + sf::kSortTile - 1) / sf::kSortTile);
   uint32_t* hist = static_cast<uint32_t*>(d_ws);
-  if (kmax < 256)
-    class_order_launch<256>(d_sizes, n, mbits, kmax, hist, ntiles, d_order, s);
-  else if (kmax < 512)
-    class_order_launch<512>(d_sizes, n, mbits, kmax, hist, ntiles, d_order, s);
-  else
-    class_order_launch<1024>(d_sizes, n, mbits, kmax, hist, ntiles, d_order, s);
-  return hip_err(hipGetLastError());
+  if (kmax < 256) return class_order_launch<256>(d_sizes, n, mbits, kmax, hist, ntiles, d_order, s);
+  if (kmax < 512) return class_order_launch<512>(d_sizes, n, mbits, kmax, hist, ntiles, d_order, s);
+  return class_order_launch<1024>(d_sizes, n, mbits, kmax, hist, ntiles, d_order, s);
 }
 
 }  // namespace sfi

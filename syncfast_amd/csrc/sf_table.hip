@@ -13,6 +13,7 @@
 #include <algorithm>
 
 #include "sf_block_hash.hpp"
+#include "sf_device.hpp"
 
 namespace sf {
 
@@ -328,14 +329,15 @@ static uint32_t* table_order(const uint32_t* d_sizes, uint64_t n, hipStream_t s,
   const unsigned kbits = mbits <= 4 ? 8u : 4u + mbits;
   const uint32_t kmax = (1u << kbits) - 1u;
   // one counting pass over 256 / 512 / 1024 classes (sf_sort.hip)
-  const size_t ob = align256(n * 4), total = ob + align256(class_order_workspace(n, kmax));
-  uint8_t* ws = nullptr;
-  if (stream_alloc(reinterpret_cast<void**>(&ws), total, s) != SF_OK) {
+  ScratchLayout L;
+  const size_t order_at = L.add(n * 4), sort_at = L.add(class_order_workspace(n, kmax));
+  void* ws = nullptr;
+  if (stream_alloc(&ws, L.total(), s) != SF_OK) {
     (void)hipGetLastError();
     return nullptr;
   }
-  uint32_t* order = reinterpret_cast<uint32_t*>(ws);
-  if (class_order(d_sizes, n, mbits, kmax, ws + ob, order, s) != SF_OK) {
+  uint32_t* order = L.at<uint32_t>(ws, order_at);
+  if (class_order(d_sizes, n, mbits, kmax, L.at<void>(ws, sort_at), order, s) != SF_OK) {
     (void)hipGetLastError();
     stream_free(ws, s);
     return nullptr;
@@ -351,14 +353,11 @@ static int launch_table_kernel(const uint8_t* d_data, uint64_t len, const uint64
                                uint32_t* weak, const uint32_t* order, hipStream_t stream) {
   const uint64_t ngroups = (nblocks + 63) / 64;
   const unsigned grid = (unsigned)((ngroups + sf::kTableWG - 1) / sf::kTableWG);
-  clear_stale_error();
   if (weak)
-    hipLaunchKernelGGL((sf::sha1_table_kernel<128, true>), dim3(grid), dim3(64 * sf::kTableWG), 0, stream, d_data, len,
-                       d_offsets, d_sizes, nblocks, d_digests, d_status, weak, order);
-  else
-    hipLaunchKernelGGL((sf::sha1_table_kernel<128, false>), dim3(grid), dim3(64 * sf::kTableWG), 0, stream, d_data, len,
-                       d_offsets, d_sizes, nblocks, d_digests, d_status, nullptr, order);
-  return hip_err(hipGetLastError());
+    return launch(sf::sha1_table_kernel<128, true>, dim3(grid), dim3(64 * sf::kTableWG), stream, d_data, len, d_offsets,
+                  d_sizes, nblocks, d_digests, d_status, weak, order);
+  return launch(sf::sha1_table_kernel<128, false>, dim3(grid), dim3(64 * sf::kTableWG), stream, d_data, len, d_offsets,
+                d_sizes, nblocks, d_digests, d_status, nullptr, order);
 }
 
 int launch_table(const void* d_data, uint64_t len, const uint64_t* d_offsets, const uint32_t* d_sizes,

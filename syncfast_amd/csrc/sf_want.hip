@@ -37,10 +37,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <rocprim/device/device_scan.hpp>
 #include <rocprim/iterator/transform_iterator.hpp>
 
-#include "sf_internal.hpp"
+#include "sf_device.hpp"
 #include "sf_want_plan.hpp"
 
 namespace {
@@ -136,8 +135,6 @@ using namespace sfi;
 
 namespace {
 
-dim3 grid_of(uint64_t n) { return dim3((unsigned)ceil_div(n, 256)); }
-
 // A block set that is given back on every path out of a call.
 struct Set {
   sf_block_set* p = nullptr;
@@ -150,26 +147,10 @@ struct Set {
 
 using Flags = rocprim::transform_iterator<const uint8_t*, IsSet, uint64_t>;
 
-int scan_bytes(size_t* tmp, hipStream_t s, uint64_t n) {
-  uint64_t* nul = nullptr;
-  if (rocprim::inclusive_scan(nullptr, *tmp, Flags(nullptr, IsSet()), nul, (size_t)n, rocprim::plus<uint64_t>(), s) !=
-      hipSuccess) {
-    (void)hipGetLastError();
-    return SF_ENODEV;
-  }
-  return SF_OK;
+// ends[i] = the flags that are 1 in flags[0 .. i]; tmp NULL: the temporary's size alone
+int scan_flags(void* tmp, size_t& tmp_bytes, const uint8_t* flags, uint64_t* ends, uint64_t n, hipStream_t s) {
+  return scan_inclusive(tmp, tmp_bytes, Flags(flags, IsSet()), ends, n, s);
 }
-
-int scan_flags(void* tmp, size_t tmp_bytes, const uint8_t* flags, uint64_t* ends, uint64_t n, hipStream_t s) {
-  if (rocprim::inclusive_scan(tmp, tmp_bytes, Flags(flags, IsSet()), ends, (size_t)n, rocprim::plus<uint64_t>(), s) !=
-      hipSuccess) {
-    (void)hipGetLastError();
-    return SF_ENODEV;
-  }
-  return SF_OK;
-}
-
-sf_wire_run* empty_run() { return new sf_wire_run{nullptr, 0, 0, -1, nullptr}; }
 
 int get_blocks(const uint8_t* d_digests, const int64_t* d_rows, const uint8_t* d_take, uint64_t n, int distinct,
                sf_wire_run** out, uint64_t* n_requests, hipStream_t s) {
@@ -179,36 +160,31 @@ int get_blocks(const uint8_t* d_digests, const int64_t* d_rows, const uint8_t* d
   if (n > kMaxRows || misaligned(d_rows, 8)) return SF_EINVAL;
   if (n && (!d_digests || misaligned(d_digests, 4))) return SF_EINVAL;
   if (n == 0) {
-    *out = empty_run();
+    *out = wire_run_empty();
     return SF_OK;
   }
-  int dev = 0;
-  SF_HIP(hipGetDevice(&dev));
   size_t tmp = 0;
-  int rc = scan_bytes(&tmp, s, n);
+  int rc = scan_flags(nullptr, tmp, nullptr, nullptr, n, s);
   if (rc != SF_OK) return rc;
   // the scan's end offsets, the lookup's rows (distinct), the flags, the scan's
-  const size_t eb = align256(n * 8), fb = align256(n);
+  ScratchLayout L;
+  const size_t ends_at = L.add(n * 8), found_at = L.add(distinct ? n * 8 : 0), ask_at = L.add(n);
   Scratch ws(s);
-  rc = stream_alloc(&ws.p, eb + (distinct ? eb : 0) + fb + tmp + 8, s);
+  rc = stream_alloc(&ws.p, L.total() + tmp + 8, s);
   if (rc != SF_OK) return rc;
-  uint8_t* w = static_cast<uint8_t*>(ws.p);
-  uint64_t* ends = reinterpret_cast<uint64_t*>(w);
-  int64_t* found = reinterpret_cast<int64_t*>(w + eb);
-  uint8_t* ask = w + eb + (distinct ? eb : 0);
-  void* scan_tmp = ask + fb;
+  uint64_t* ends = L.at<uint64_t>(ws.p, ends_at);
+  int64_t* found = L.at<int64_t>(ws.p, found_at);
+  uint8_t* ask = L.at<uint8_t>(ws.p, ask_at);
+  void* scan_tmp = L.at<void>(ws.p, L.total());
 
-  clear_stale_error();
-  hipLaunchKernelGGL(want_ask_kernel, grid_of(n), dim3(256), 0, s, d_rows, d_take, n, ask);
-  SF_HIP(hipGetLastError());
+  rc = launch(want_ask_kernel, grid256(n), dim3(256), s, d_rows, d_take, n, ask);
+  if (rc != SF_OK) return rc;
   if (distinct) {
     Set set(s);
     rc = sf_block_set_build(d_digests, ask, n, &set.p, s);
     if (rc == SF_OK) rc = sf_block_set_lookup(set.p, d_digests, n, found, s);
+    if (rc == SF_OK) rc = launch(want_first_kernel, grid256(n), dim3(256), s, found, n, ask);
     if (rc != SF_OK) return rc;
-    clear_stale_error();
-    hipLaunchKernelGGL(want_first_kernel, grid_of(n), dim3(256), 0, s, found, n, ask);
-    SF_HIP(hipGetLastError());
   }
   rc = scan_flags(scan_tmp, tmp, ask, ends, n, s);
   if (rc != SF_OK) return rc;
@@ -216,28 +192,16 @@ int get_blocks(const uint8_t* d_digests, const int64_t* d_rows, const uint8_t* d
   SF_HIP(hipMemcpyAsync(&count, ends + n - 1, 8, hipMemcpyDeviceToHost, s));
   SF_HIP(hipStreamSynchronize(s));
   if (count == 0) {
-    *out = empty_run();
+    *out = wire_run_empty();
     return SF_OK;
   }
 
-  sf_wire_run* run = new sf_wire_run{nullptr, count * sfwp::kGetBlock, count, dev, nullptr};
-  rc = stream_alloc(reinterpret_cast<void**>(&run->bytes), run->n_bytes, s);
-  if (rc == SF_OK) rc = hip_err(hipEventCreateWithFlags(&run->done, hipEventDisableTiming));
-  if (rc == SF_OK) {
-    clear_stale_error();
-    hipLaunchKernelGGL(want_emit_kernel, grid_of(n), dim3(256), 0, s, d_digests, ask, ends, n, run->bytes);
-    rc = hip_err(hipGetLastError());
-  }
-  if (rc == SF_OK) rc = hip_err(hipEventRecord(run->done, s));
-  if (rc != SF_OK) {
-    stream_free(run->bytes, s);
-    if (run->done) (void)hipEventDestroy(run->done);
-    delete run;
-    return rc;
-  }
-  *out = run;
-  if (n_requests) *n_requests = count;
-  return SF_OK;
+  sf_wire_run* run = nullptr;
+  rc = wire_run_begin(count * sfwp::kGetBlock, count, s, &run);
+  if (rc == SF_OK) rc = launch(want_emit_kernel, grid256(n), dim3(256), s, d_digests, ask, ends, n, run->bytes);
+  rc = wire_run_finish(run, rc, s, out);
+  if (rc == SF_OK && n_requests) *n_requests = count;
+  return rc;
 }
 
 int place_block_data(const uint8_t* d_row_digests, const uint32_t* d_row_sizes, const uint64_t* d_row_dst,
@@ -262,20 +226,20 @@ int place_block_data(const uint8_t* d_row_digests, const uint32_t* d_row_sizes, 
   }
   const bool have = n_msgs != 0;
   size_t tmp = 0;
-  int rc = have ? scan_bytes(&tmp, s, n_rows) : SF_OK;
+  int rc = have ? scan_flags(nullptr, tmp, nullptr, nullptr, n_rows, s) : SF_OK;
   if (rc != SF_OK) return rc;
   // end offsets with the two counters behind them (read back together), the
   // lookup's messages, the rows' classes, the scan's
-  const size_t eb = align256((n_rows + 2) * 8), fb = align256(n_rows * 8), cb = align256(n_rows);
+  ScratchLayout L;
+  const size_t ends_at = L.add((n_rows + 2) * 8), found_at = L.add(n_rows * 8), cls_at = L.add(n_rows);
   Scratch ws(s);
-  rc = stream_alloc(&ws.p, eb + fb + cb + tmp + 8, s);
+  rc = stream_alloc(&ws.p, L.total() + tmp + 8, s);
   if (rc != SF_OK) return rc;
-  uint8_t* w = static_cast<uint8_t*>(ws.p);
-  uint64_t* ends = reinterpret_cast<uint64_t*>(w);
+  uint64_t* ends = L.at<uint64_t>(ws.p, ends_at);
   unsigned long long* counters = reinterpret_cast<unsigned long long*>(ends + n_rows);
-  int64_t* found = reinterpret_cast<int64_t*>(w + eb);
-  uint8_t* cls = w + eb + fb;
-  void* scan_tmp = cls + cb;
+  int64_t* found = L.at<int64_t>(ws.p, found_at);
+  uint8_t* cls = L.at<uint8_t>(ws.p, cls_at);
+  void* scan_tmp = L.at<void>(ws.p, L.total());
   SF_HIP(hipMemsetAsync(counters, 0, 16, s));
   if (have) {
     Set set(s);
@@ -283,10 +247,9 @@ int place_block_data(const uint8_t* d_row_digests, const uint32_t* d_row_sizes, 
     if (rc == SF_OK) rc = sf_block_set_lookup(set.p, d_row_digests, n_rows, found, s);
     if (rc != SF_OK) return rc;
   }
-  clear_stale_error();
-  hipLaunchKernelGGL(place_class_kernel, grid_of(n_rows), dim3(256), 0, s, d_row_present, d_row_sizes,
-                     have ? found : nullptr, d_msg_sizes, n_rows, cls, counters);
-  SF_HIP(hipGetLastError());
+  rc = launch(place_class_kernel, grid256(n_rows), dim3(256), s, d_row_present, d_row_sizes, have ? found : nullptr,
+              d_msg_sizes, n_rows, cls, counters);
+  if (rc != SF_OK) return rc;
   uint64_t back[3] = {0, 0, 0};  // the jobs, the rows that wait, the size mismatches
   if (have) {
     rc = scan_flags(scan_tmp, tmp, cls, ends, n_rows, s);
@@ -305,14 +268,9 @@ int place_block_data(const uint8_t* d_row_digests, const uint32_t* d_row_sizes, 
   }
   *n_left = back[1] - jobs;
   if (d_msg_uses && n_msgs) SF_HIP(hipMemsetAsync(d_msg_uses, 0, n_msgs * 4, s));
-  if (jobs) {
-    clear_stale_error();
-    hipLaunchKernelGGL(place_emit_kernel, grid_of(n_rows), dim3(256), 0, s, cls, ends, found, d_row_sizes, d_row_dst,
-                       d_msg_off, n_rows, d_row_present, d_src_off, d_dst_off, d_sizes, d_job_rows, d_job_msgs,
-                       d_msg_uses);
-    SF_HIP(hipGetLastError());
-  }
-  return SF_OK;
+  if (!jobs) return SF_OK;
+  return launch(place_emit_kernel, grid256(n_rows), dim3(256), s, cls, ends, found, d_row_sizes, d_row_dst, d_msg_off,
+                n_rows, d_row_present, d_src_off, d_dst_off, d_sizes, d_job_rows, d_job_msgs, d_msg_uses);
 }
 
 }  // namespace

@@ -15,8 +15,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <rocprim/device/device_scan.hpp>
-
+#include "sf_device.hpp"
 #include "sf_launch.hpp"
 
 namespace {
@@ -115,10 +114,7 @@ int launch_wire(const uint8_t* d_digests, uint64_t n, uint32_t bs, uint32_t last
     }
     return SF_OK;
   }
-  clear_stale_error();
-  hipLaunchKernelGGL(sf::wire_file_blocks_kernel, dim3((unsigned)ceil_div(n, 256)), dim3(256), 0, stream, d_digests,
-                     n, bs, last, d_out);
-  return hip_err(hipGetLastError());
+  return launch(sf::wire_file_blocks_kernel, grid256(n), dim3(256), stream, d_digests, n, bs, last, d_out);
 }
 
 // The end offset of every message of the run (inclusive scan of the
@@ -127,34 +123,22 @@ int launch_wire(const uint8_t* d_digests, uint64_t n, uint32_t bs, uint32_t last
 int wire_plan(const uint32_t* d_sizes, uint64_t n, uint64_t** d_ends, hipStream_t s) {
   *d_ends = nullptr;
   size_t tmp = 0;
-  uint64_t* nul = nullptr;
-  if (rocprim::inclusive_scan(nullptr, tmp, nul, nul, (size_t)n, rocprim::plus<uint64_t>(), s) != hipSuccess) {
-    (void)hipGetLastError();
-    return SF_ENODEV;
-  }
-  const size_t lb = (n * 8 + 255) & ~(size_t)255;
-  uint8_t* ws = nullptr;  // ends first (returned), then lengths and the scan's temporary
-  {
-    const int arc = stream_alloc(reinterpret_cast<void**>(&ws), 2 * lb + tmp + 8, s);
-    if (arc != SF_OK) return arc;
-  }
-  uint64_t* ends = reinterpret_cast<uint64_t*>(ws);
-  uint64_t* lens = reinterpret_cast<uint64_t*>(ws + lb);
-  int rc = SF_OK;
+  uint64_t* const nul = nullptr;
+  int rc = scan_inclusive(nullptr, tmp, nul, nul, n, s);
+  if (rc != SF_OK) return rc;
+  // ends first (returned), then lengths and the scan's temporary
+  ScratchLayout L;
+  const size_t ends_at = L.add(n * 8), lens_at = L.add(n * 8);
+  void* ws = nullptr;
+  if ((rc = stream_alloc(&ws, L.total() + tmp + 8, s)) != SF_OK) return rc;
+  uint64_t* ends = L.at<uint64_t>(ws, ends_at);
+  uint64_t* lens = L.at<uint64_t>(ws, lens_at);
   // pieces of at most 2^30 messages per launch: a grid past 2^32 work-items
   // is not launched whole
-  for (uint64_t first = 0; first < n && rc == SF_OK; first += kWireMaxPerLaunch) {
-    const uint64_t cnt = std::min(kWireMaxPerLaunch, n - first);
-    sfi::clear_stale_error();
-    hipLaunchKernelGGL(wire_len_kernel, dim3((unsigned)ceil_div(cnt, 256)), dim3(256), 0, s, d_sizes + first, cnt,
-                       lens + first);
-    rc = hip_err(hipGetLastError());
-  }
-  if (rc == SF_OK &&
-      rocprim::inclusive_scan(ws + 2 * lb, tmp, lens, ends, (size_t)n, rocprim::plus<uint64_t>(), s) != hipSuccess) {
-    (void)hipGetLastError();
-    rc = SF_ENODEV;
-  }
+  rc = for_pieces(n, kWireMaxPerLaunch, [&](uint64_t first, uint64_t cnt) {
+    return launch(wire_len_kernel, grid256(cnt), dim3(256), s, d_sizes + first, cnt, lens + first);
+  });
+  if (rc == SF_OK) rc = scan_inclusive(L.at<void>(ws, L.total()), tmp, lens, ends, n, s);
   if (rc != SF_OK) {
     stream_free(ws, s);
     return rc;
@@ -166,25 +150,17 @@ int wire_plan(const uint32_t* d_sizes, uint64_t n, uint64_t** d_ends, hipStream_
 // d_chunk_ends[k] = end offset of chunk k (chunks of `per` messages).
 int wire_chunk_ends(const uint64_t* d_ends, uint64_t n, uint64_t per, uint64_t* d_chunk_ends, hipStream_t s) {
   const uint64_t nchunks = ceil_div(n, per);
-  sfi::clear_stale_error();
-  hipLaunchKernelGGL(wire_chunk_ends_kernel, dim3((unsigned)ceil_div(nchunks, 256)), dim3(256), 0, s, d_ends, n, per,
-                     nchunks, d_chunk_ends);
-  return hip_err(hipGetLastError());
+  return launch(wire_chunk_ends_kernel, grid256(nchunks), dim3(256), s, d_ends, n, per, nchunks, d_chunk_ends);
 }
 
 // Messages [first, first + cnt) of a planned run, written from the start of
 // d_out (base = the end offset of message first - 1, 0 for the first).
 int wire_build(const uint8_t* d_digests, const uint32_t* d_sizes, const uint64_t* d_ends, uint64_t first,
                uint64_t cnt, uint64_t base, uint8_t* d_out, hipStream_t s) {
-  for (uint64_t a = 0; a < cnt; a += kWireMaxPerLaunch) {
-    const uint64_t m = std::min(kWireMaxPerLaunch, cnt - a);
-    sfi::clear_stale_error();
-    hipLaunchKernelGGL(wire_blocks_kernel, dim3((unsigned)ceil_div(m, 256)), dim3(256), 0, s,
-                       d_digests + (first + a) * 20, d_sizes + first + a, d_ends + first + a, m, base, d_out);
-    const int rc = hip_err(hipGetLastError());
-    if (rc != SF_OK) return rc;
-  }
-  return SF_OK;
+  return for_pieces(cnt, kWireMaxPerLaunch, [&](uint64_t a, uint64_t m) {
+    return launch(wire_blocks_kernel, grid256(m), dim3(256), s, d_digests + (first + a) * 20, d_sizes + first + a,
+                  d_ends + first + a, m, base, d_out);
+  });
 }
 
 }  // namespace sfi
