@@ -12,6 +12,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from syncfast_amd import host  # noqa: E402
+from syncfast_amd._lib import set_knob  # noqa: E402
 
 GiB = 1 << 30
 
@@ -37,18 +38,22 @@ def main():
     # in place (regions locked one ahead, rows + blocks_hash overlapped), in
     # place serial (whole range locked first, rows after: the earlier form),
     # staged through pinned buffers
-    routes = (("in place, overlapped", {}), ("in place, serial", {"SF_INPLACE_SERIAL": "1"}),
-              ("staged memcpy", {"SF_NO_HOSTREG": "1"}))
-    for rep in range(2):
-        for name, env in routes:
-            os.environ.update(env)
+    # (knobs are latched when the library loads: set through the test hook)
+    routes = (("in place, overlapped", None), ("in place, serial", "SF_INPLACE_SERIAL"),
+              ("staged memcpy", "SF_NO_HOSTREG"))
+    for rep in range(int(os.environ.get("E2E_REPS", "2"))):
+        for name, knob in routes:
+            if knob:
+                set_knob(knob, 1)
             t0 = time.perf_counter()
             rows = host.index_buffer(data, 4096)
             t = time.perf_counter() - t0
-            for k in env:
-                del os.environ[k]
+            if knob:
+                set_knob(knob, 0)
             print(f"sf_index_buffer {n / GiB:.0f} GiB, 4 KiB blocks, {name} (rep {rep}):", rate(n, t), flush=True)
     assert rows.shape[0] == n // 4096
+    if os.environ.get("E2E_ONLY") == "buffer":
+        return
     d = os.environ.get("E2E_DIR", "/tmp")
     with tempfile.NamedTemporaryFile(dir=d, delete=False) as f:
         f.write(data.tobytes())
@@ -72,7 +77,6 @@ def wire_rate():
     """FILE_BLOCK run of config 2's table (2^21 blocks) streamed to a file
     descriptor (/dev/null: device build + D2H + write syscalls)."""
     from syncfast_amd import device, wire
-    from syncfast_amd._lib import set_knob
     n = 8 << 30
     t = device.splitmix_tensor(n, 0x5EED0000)
     dig = device.index_device(t, 4096)

@@ -16,9 +16,14 @@
 //   sf_match.hip  digest lookup; sf_litmus.hip  a memory-model probe;
 //   sf_batch.cpp  the device-resident batch entry points (host planning over
 //                 the launchers);
-//   sf_host.cpp  the host-memory entry points: per-device cache of streams
-//                 and staging buffers, the buffer / file / fd / range
-//                 pipelines, the wire stream, host SHA-1 helpers;
+//   sf_host.cpp   the host-memory indexing entry points: per-device cache of
+//                 streams and staging buffers, the buffer / file / fd / range
+//                 pipelines, stamp and host SHA-1 helpers;
+//   sf_host_out.cpp  the device-to-descriptor writers: FILE_BLOCK runs,
+//                 device bytes and BLOCK_DATA runs streamed to an fd;
+//   sf_pagelock.cpp  the registry of host ranges page-locked by the in-place
+//                 routes (the region rule itself is sf_inplace.hpp: host
+//                 arithmetic, executed by tests/native/inplace_regions.cpp);
 //   sf_files.cpp  sf_index_files, the many-file pipeline;
 //   sf_fds.cpp    sf_index_fds_blocks, the default mode over many files;
 //   sf_multi.cpp  one process, N devices;
@@ -83,7 +88,7 @@
   } while (0)
 
 // The opaque handle of include/syncfast_amd.h: a BLOCK_DATA run built in HBM
-// (sf_send.hip builds and frees it, sf_host.cpp streams it to a descriptor).
+// (sf_send.hip builds and frees it, sf_host_out.cpp streams it to a descriptor).
 // bytes: stream-ordered scratch of `device` (NULL for an empty run, which
 // needs no device); done: recorded on the building stream behind the last
 // kernel that writes the run (NULL for an empty run).

@@ -1,11 +1,13 @@
-// sf_stage.hpp -- what the host pipelines share (sf_host.cpp, sf_files.cpp,
-// sf_fds.cpp, sf_cut.cpp, sf_cdc.hip): the two-stage driver, the file reader
-// and its sliced form, the checks and windows of an explicit list, the rows of
-// a malloc'd result, the named slots of the per-device buffer cache and the
-// stamp bracket of the descriptor routes.
+// sf_stage.hpp -- what the host pipelines share (sf_host.cpp, sf_host_out.cpp,
+// sf_files.cpp, sf_fds.cpp, sf_cut.cpp, sf_cdc.hip): the two-stage driver, the
+// file reader and its sliced form, the checks and windows of an explicit list,
+// the rows of a malloc'd result, the named slots of the per-device buffer
+// cache, the stamp bracket of the descriptor routes and the page-lock
+// registry of the in-place routes.
 // No HIP here: what needs the runtime or the worker threads is declared and
-// lives in sf_stage.cpp, sf_host.cpp and sf_pool.cpp, so a stand-alone program
-// can test the templates on a CPU (tests/native/stage_driver.cpp).
+// lives in sf_stage.cpp, sf_host.cpp, sf_pagelock.cpp and sf_pool.cpp, so a
+// stand-alone program can test the templates on a CPU
+// (tests/native/stage_driver.cpp).
 // sf_internal.hpp includes this header.
 #pragma once
 #include <errno.h>
@@ -23,6 +25,7 @@
 
 #include "../../include/syncfast_amd.h"
 #include "host_sha1.h"
+#include "sf_inplace.hpp"
 
 namespace sfi __attribute__((visibility("hidden"))) {
 
@@ -71,6 +74,13 @@ inline bool read_fully(int fd, uint8_t* dst, uint64_t pos, uint64_t want) {
   }
   return true;
 }
+
+// A descriptor the call opened itself: closed on every return, and if an
+// exception unwinds (to guarded(), in an entry point).
+struct Fd {
+  int fd;
+  ~Fd() { if (fd >= 0) close(fd); }
+};
 
 // read_fully's write twin: src[0, want) to bytes [pos, pos + want) of fd
 // (pwrite: the position is not used or moved), EINTR tried again.  false: an
@@ -204,6 +214,19 @@ inline int read_sliced(int fd, uint8_t* dst, uint64_t pos, uint64_t n) {
 // Defined in sf_host.cpp.
 bool stamp_of(int fd, sf_file_stamp* s, mode_t* mode);
 bool same_stamp(const sf_file_stamp& a, const sf_file_stamp& b);
+
+// The process-wide registry of host ranges this library page-locked
+// (sf_pagelock.cpp), behind the lock / unlock of InplaceRegions.  lock_pages
+// page-locks [a, e) (page edges) if it is private anonymous memory that no
+// concurrent call of ours has locked -- a file mapping never is; the counters
+// pages_locked and not_anon_refused record what it did -- and unlock_pages
+// undoes one lock_pages by its start.  range_locked_by_us: [a, e) overlaps a
+// range of the registry.  pinned_by_hip: the HIP runtime knows both ends of
+// [a, e) as page-locked host memory (hipHostMalloc, hipHostRegister).
+PageLock lock_pages(uintptr_t a, uintptr_t e);
+void unlock_pages(uintptr_t a);
+bool range_locked_by_us(uintptr_t a, uintptr_t e);
+bool pinned_by_hip(uintptr_t a, uintptr_t e);
 
 // HostRes slots, device and pinned alike: the two stages' bytes; the digest
 // table of one whole file (the in-place route); the two stages' digests; the

@@ -242,6 +242,35 @@ def test_index_buffer_inplace_routes(gpu, inplace_case, knob, knobs):
     assert rows["offset"][-1] == (n - 1) // 4096 * 4096 and int(rows["size"].sum()) == n
 
 
+@pytest.fixture(scope="module")
+def inplace_small_case():
+    # the same shape at 1 MiB stages: 2.5 stages + a ragged tail, from data[3:]
+    n = 5 * (1 << 20) // 2 + 4093
+    data = oracle.splitmix_bytes(n + 3, 196)
+    return data, {bs: oracle.index_fixed(data[3:], bs) for bs in (4096, 1000)}
+
+
+@pytest.mark.parametrize("bs", [4096, 1000])
+@pytest.mark.parametrize("knob", [("", ""), ("SF_INPLACE_SERIAL", "1"), ("SF_TEST_INPLACE_FAIL_AT", "0"),
+                                  ("SF_TEST_INPLACE_FAIL_AT", "1"), ("SF_TEST_INPLACE_FAIL_AT", "2")])
+def test_index_buffer_inplace_routes_small_stages(gpu, inplace_small_case, knob, bs, knobs):
+    # test_index_buffer_inplace_routes in small: SF_TEST_STREAM_STAGE_MIB=1
+    # makes the in-place route's stages 1 MiB, so 2.6 MiB is three regions.  At
+    # block size 1000 a stage is 1,048,000 bytes: every stage after the first
+    # starts mid-page and has a head in the previous region.
+    knobs.set("SF_TEST_STREAM_STAGE_MIB", 1)
+    if knob[0]:
+        knobs.set(knob[0], int(knob[1]))
+    data, want = inplace_small_case
+    offs, sizes, sha = want[bs]
+    locked = _lib.get_stat("pages_locked")
+    rows = host.index_buffer(data[3:], bs)
+    assert np.array_equal(rows["sha1"], sha)
+    assert np.array_equal(rows["offset"], offs) and np.array_equal(rows["size"], sizes)
+    if not knob[0]:  # the small stages really reached the in-place route: one lock per region
+        assert _lib.get_stat("pages_locked") - locked >= 2
+
+
 def test_index_buffer_already_pinned(gpu, inplace_case):
     # a caller buffer that is already page-locked (torch pinned memory =
     # hipHostMalloc): hipHostRegister reports it registered, and the stages
