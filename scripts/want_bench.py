@@ -44,7 +44,7 @@ import torch  # noqa: E402
 
 from copy_blocks_bench import cdc_sizes  # noqa: E402
 from syncfast_amd import _lib, device, wire  # noqa: E402
-from syncfast_amd.index import Index  # noqa: E402
+from syncfast_amd.index import INSERT_BLOCK, Index  # noqa: E402
 
 
 def main():
@@ -86,8 +86,7 @@ def main():
         idx = Index.open_in_memory()
         fid = idx.add_temp_file("new.bin")
         idx.begin()
-        idx.db.executemany("INSERT INTO blocks(hash, file_id, offset, size, present) VALUES(?, ?, ?, ?, 0);",
-                           ((h, fid, int(o), int(s)) for h, o, s in zip(hexes, row_off, sz)))
+        idx.db.executemany(INSERT_BLOCK, ((h, fid, int(o), int(s), 0) for h, o, s in zip(hexes, row_off, sz)))
         idx.commit()
         return idx
     t_req, t_apply, n_writes = [], [], 0

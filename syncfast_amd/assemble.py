@@ -28,12 +28,6 @@ from .index import _name_str
 __all__ = ["FileImages"]
 
 
-def _upload(data: bytes, dev: torch.device) -> torch.Tensor:
-    if not data:
-        return torch.empty(0, dtype=torch.uint8, device=dev)
-    return torch.frombuffer(bytearray(data), dtype=torch.uint8).to(dev)
-
-
 def _rounds(jobs: List[tuple]) -> List[List[tuple]]:
     """jobs = [(src_offset, dst_offset, size > 0)] in the order the reference
     would write them, split into calls of disjoint destinations: a job that
@@ -78,8 +72,7 @@ class FileImages:
     ALIGN = 256
 
     def __init__(self, sizes: Mapping, device=None, root=None):
-        self.device = torch.device(device) if device is not None else \
-            torch.device("cuda", torch.cuda.current_device())
+        self.device = _device.device_of(device)
         self.root = Path(root) if root is not None else None
         self._base: Dict[str, int] = {}
         self._size: Dict[str, int] = {}
@@ -149,7 +142,7 @@ class FileImages:
         too.  A write that ends past its file's size raises ValueError before
         anything is launched -- the reference would grow the file; an image
         has the size FILE_END fixed.  Returns the number of copy calls."""
-        src = data if isinstance(data, torch.Tensor) else _upload(bytes(data), self.device)
+        src = data if isinstance(data, torch.Tensor) else _device.upload(bytes(data), self.device)
         last: Dict[tuple, tuple] = {}
         for name, offset, start, size in writes:
             offset, start, size = int(offset), int(start), int(size)
@@ -190,7 +183,7 @@ class FileImages:
         if key not in self._local:
             if self.root is None:
                 raise ValueError("no root to read local files from: pass root= or source=")
-            self._local[key] = _upload(np.fromfile(self.root / key, dtype=np.uint8).tobytes(), self.device)
+            self._local[key] = _device.upload(np.fromfile(self.root / key, dtype=np.uint8).tobytes(), self.device)
         return self._local[key]
 
     def apply_copies(self, name, copies, source: Optional[Callable] = None,

@@ -33,6 +33,7 @@ __all__ = [
     "fill_splitmix", "splitmix_tensor", "BlockSet", "index_device_multi",
     "cut_device_zpaq", "index_device_zpaq", "zpaq_segment_len", "zpaq_device_stats",
     "copy_blocks", "copy_stats", "write_to_fd", "get_block_requests", "place_block_data",
+    "device_of", "upload",
 ]
 
 
@@ -47,6 +48,20 @@ def _require_device(t: torch.Tensor, name: str, dtype=None, device: Optional[tor
         raise TypeError(f"{name} must be {dtype} (got {t.dtype})")
     if not t.is_contiguous():
         raise ValueError(f"{name} must be contiguous")
+
+
+def device_of(device=None) -> torch.device:
+    """``device`` as a torch.device; None: the current ROCm device."""
+    return torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+
+
+def upload(data, device=None) -> torch.Tensor:
+    """Bytes as a flat uint8 HBM tensor on ``device`` (``device_of``): a
+    received buffer, a local file's bytes, a digest list."""
+    dev = device_of(device)
+    if not data:
+        return torch.empty(0, dtype=torch.uint8, device=dev)
+    return torch.frombuffer(bytearray(data), dtype=torch.uint8).to(dev)
 
 
 def _stream_ptr(t: torch.Tensor, stream: Optional[torch.cuda.Stream]) -> int:

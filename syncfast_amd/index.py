@@ -52,7 +52,9 @@ returns them for ``WHERE file_id = ?`` with no ORDER BY (src/index.rs:663-
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
+import itertools
 import logging
 import os
 import sqlite3
@@ -105,6 +107,10 @@ SCHEMA = """
     PRAGMA user_version=0x00000000;
 """
 
+# add_block / add_missing_block (src/index.rs:387-408, 433-451): the last
+# parameter is the present flag
+INSERT_BLOCK = "INSERT INTO blocks(hash, file_id, offset, size, present) VALUES(?, ?, ?, ?, ?);"
+
 INDEX_FILE_NAME = ".syncfast.idx"  # src/index.rs:699, src/main.rs:117
 TEMP_PREFIX = ".syncfast_tmp_"     # src/lib.rs:152
 
@@ -142,6 +148,11 @@ def _mtime(f) -> DateTimeUtc:
     """``file.metadata()?.modified()?.into()`` (src/index.rs:616-619): the open
     file's mtime, to the nanosecond."""
     return DateTimeUtc.from_ns(os.fstat(f.fileno()).st_mtime_ns)
+
+
+def _stamp_mtime(stamp) -> DateTimeUtc:
+    """``_mtime`` from a stamp (host.file_stamp) of the open file."""
+    return DateTimeUtc.from_ns(stamp.mtime_sec * 10**9 + stamp.mtime_nsec)
 
 
 def _stamp_moved(fd: int, stamp) -> bool:
@@ -285,6 +296,42 @@ def _offsets(sizes) -> np.ndarray:
     return offs
 
 
+def _cut_stamped(fn: Callable, f, stamp) -> Optional[List[int]]:
+    """The stream chunker ``fn`` over the open, stamped regular file ``f``:
+    its block sizes, checked against the stamp's size, or None if the file
+    was written while it was cut."""
+    sizes = [int(x) for x in fn(f)]
+    if sum(sizes) != stamp.size and _stamp_moved(f.fileno(), stamp):
+        return None
+    return _sizes_ok(sizes, stamp.size)
+
+
+def _stop_error(stop: int, consumed: int, what: str, refused: bool, why: str) -> None:
+    """Raise the wire.ProtocolError for what stopped a device parse after
+    ``consumed`` bytes: bytes the parser raises on in ``what``, or a stop the
+    caller's state ``refused`` (``why``)."""
+    from . import wire
+    if stop == wire.SF_WIRE_MALFORMED:
+        raise wire.ProtocolError("Malformed %s at byte %d" % (what, consumed))
+    if refused:
+        raise wire.ProtocolError("%s (byte %d)" % (why, consumed))
+
+
+class _FdBatch(contextlib.ExitStack):
+    """The files of one sf_index_fds_blocks call and the owner of their open
+    descriptors: ``entries`` holds (file_id, path, name, open file, stamp,
+    future of its cut) in walk order; ``close()`` -- or leaving the batch --
+    closes the files and leaves it empty, to be filled again."""
+
+    def __init__(self):
+        super().__init__()
+        self.entries, self.nbytes = [], 0
+
+    def close(self) -> None:
+        super().close()
+        self.entries, self.nbytes = [], 0
+
+
 def read_block(path, offset: int, size: int) -> bytes:
     """The bytes of one block row: `size` bytes at `offset`.
 
@@ -396,18 +443,43 @@ class Index:
         index's rows in rowid order go to the GPU as a hash table, and each
         hash gets the row get_block would return (present, joined to a file,
         first in rowid order), or None."""
-        import torch
-
-        from .device import BlockSet
-        rows, table, present = self._lookup_table()
+        from .device import upload
         if not hashes:
             return []
-        dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        q = np.frombuffer(b"".join(h.bytes for h in hashes), np.uint8).reshape(-1, 20)
-        t = torch.from_numpy(table.copy()).to(dev)
-        with BlockSet(t, torch.from_numpy(present).to(dev)) as bset:
-            found = bset.lookup(torch.from_numpy(q.copy()).to(dev)).cpu().numpy()
+        with self._block_set(device) as (rows, bset):
+            q = upload(b"".join(h.bytes for h in hashes), bset.table.device).reshape(-1, 20)
+            found = bset.lookup(q).cpu().numpy()
         return [None if r < 0 else (PurePath(rows[r][2]), int(rows[r][3]), int(rows[r][4])) for r in found]
+
+    @contextlib.contextmanager
+    def _block_set(self, device):
+        """(rows, BlockSet): ``_lookup_table()`` as a lookup on ``device``
+        (None: the current one), closed on leaving."""
+        import torch
+
+        from .device import BlockSet, device_of
+        rows, table, present = self._lookup_table()
+        dev = device_of(device)
+        with BlockSet(torch.from_numpy(table.copy()).to(dev), torch.from_numpy(present).to(dev)) as bset:
+            yield rows, bset
+
+    def _store_received(self, rows, ids, closed, block_file, digests, offsets, sizes, found):
+        """The database half of a received FILE_BLOCK stream: block k belongs
+        to file ``ids[block_file[k]]`` and was found in row ``found[k]`` of the
+        lookup's ``rows`` (or not: < 0).  ONE executemany inserts every block
+        with its present flag, ``closed`` = [(file_id, size)] get their size
+        and blocks_hash, and the blocks found come back as one copy list per
+        entry of ``ids``, [(from_name, from_offset, to_offset, size)]."""
+        self.begin()
+        self.db.executemany(INSERT_BLOCK, ((bytes(d).hex(), ids[f], int(o), int(s), int(q >= 0))
+                                           for d, f, o, s, q in zip(digests, block_file, offsets, sizes, found)))
+        for file_id, size in closed:
+            self.set_file_size_and_compute_blocks_hash(file_id, size)
+        copies = [[] for _ in ids]
+        for f, o, s, q in zip(block_file, offsets, sizes, found):
+            if q >= 0:
+                copies[f].append((PurePath(rows[q][2]), int(rows[q][3]), int(o), int(s)))
+        return copies
 
     def receive_file_blocks(self, file_id: int, data, device=None) -> List[Tuple[PurePath, int, int, int]]:
         """The sink's GetFiles state for one incoming file
@@ -426,30 +498,17 @@ class Index:
         before ``commit()``, as the reference copies each block before its
         add_block.  A run that does not end with FILE_END right after its
         last FILE_BLOCK raises wire.ProtocolError, and nothing is written."""
-        import torch
-
         from . import wire
-        from .device import BlockSet
+        from .device import upload
         data = bytes(data)
-        rows, table, present = self._lookup_table()
-        dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        run = torch.frombuffer(bytearray(data), dtype=torch.uint8).to(dev) if data else \
-            torch.empty(0, dtype=torch.uint8, device=dev)
-        with BlockSet(torch.from_numpy(table.copy()).to(dev), torch.from_numpy(present).to(dev)) as bset:
-            digests, sizes, offsets, found, consumed, stop, end_offset = bset.receive(run)
-            digests, sizes = digests.cpu().numpy(), sizes.cpu().numpy()
-            offsets, found = offsets.cpu().numpy(), found.cpu().numpy()
-        if stop == wire.SF_WIRE_MALFORMED:
-            raise wire.ProtocolError("Malformed FILE_BLOCK run at byte %d" % consumed)
-        if stop != wire.SF_WIRE_OTHER or data[consumed:] != b"FILE_END\n":
-            raise wire.ProtocolError("FILE_BLOCK run does not end with FILE_END (byte %d)" % consumed)
-        self.begin()
-        self.db.executemany(
-            "INSERT INTO blocks(hash, file_id, offset, size, present) VALUES(?, ?, ?, ?, ?);",
-            ((bytes(d).hex(), file_id, int(o), int(s), int(r >= 0)) for d, o, s, r in zip(digests, offsets, sizes, found)))
-        self.set_file_size_and_compute_blocks_hash(file_id, end_offset)
-        return [(PurePath(rows[r][2]), int(rows[r][3]), int(o), int(s))
-                for o, s, r in zip(offsets, sizes, found) if r >= 0]
+        with self._block_set(device) as (rows, bset):
+            r = bset.receive(upload(data, bset.table.device))
+            digests, sizes, offsets, found = (t.cpu().numpy() for t in r[:4])
+        consumed, stop, end_offset = r[4:]
+        _stop_error(stop, consumed, "FILE_BLOCK run", stop != wire.SF_WIRE_OTHER or data[consumed:] != b"FILE_END\n",
+                    "FILE_BLOCK run does not end with FILE_END")
+        return self._store_received(rows, [file_id], [(file_id, end_offset)], [0] * len(found),
+                                    digests, offsets, sizes, found)[0]
 
     def receive_files(self, data, device=None, open_file=None):
         """The sink's GetFiles state (src/sync/fs.rs:449-500) for a buffer of
@@ -486,23 +545,16 @@ class Index:
         them, or None.  Bytes the parser raises on, a message the sink's state
         does not take, or another command right after the accepted messages
         raise wire.ProtocolError; in every raising case nothing is written."""
-        import torch
-
         from . import wire
-        from .device import BlockSet
+        from .device import upload
         data = bytes(data)
-        rows, table, present = self._lookup_table()
-        dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        run = torch.frombuffer(bytearray(data), dtype=torch.uint8).to(dev) if data else \
-            torch.empty(0, dtype=torch.uint8, device=dev)
-        with BlockSet(torch.from_numpy(table.copy()).to(dev), torch.from_numpy(present).to(dev)) as bset:
-            r = bset.receive_files(run, open=open_file is not None, base_offset=open_file[1] if open_file else 0)
+        with self._block_set(device) as (rows, bset):
+            r = bset.receive_files(upload(data, bset.table.device), open=open_file is not None,
+                                   base_offset=open_file[1] if open_file else 0)
             digests, sizes, offsets, found, block_file, name_at, name_len, _first, file_size = (
                 t.cpu().numpy() for t in r[:9])
-        if r.stop == wire.SF_WIRE_MALFORMED:
-            raise wire.ProtocolError("Malformed GetFiles stream at byte %d" % r.consumed)
-        if r.stop in (wire.SF_WIRE_UNEXPECTED, wire.SF_WIRE_OTHER):
-            raise wire.ProtocolError("Unexpected message from source (byte %d)" % r.consumed)
+        _stop_error(r.stop, r.consumed, "GetFiles stream", r.stop in (wire.SF_WIRE_UNEXPECTED, wire.SF_WIRE_OTHER),
+                    "Unexpected message from source")
         ids = []
         for at, n in zip(name_at.tolist(), name_len.tolist()):
             if at < 0:  # the file carried in
@@ -517,17 +569,11 @@ class Index:
                 raise SyncfastError("Unknown file %r" % name)
             ids.append(temp[0])
         names = [self.get_file_name(i) for i in ids]
-        copies = {name: [] for name in names}
-        self.begin()
-        self.db.executemany(
-            "INSERT INTO blocks(hash, file_id, offset, size, present) VALUES(?, ?, ?, ?, ?);",
-            ((bytes(d).hex(), ids[f], int(o), int(s), int(q >= 0))
-             for d, f, o, s, q in zip(digests, block_file, offsets, sizes, found)))
-        for f in range(len(ids) - 1 if r.open else len(ids)):
-            self.set_file_size_and_compute_blocks_hash(ids[f], int(file_size[f]))
-        for f, o, s, q in zip(block_file, offsets, sizes, found):
-            if q >= 0:
-                copies[names[f]].append((PurePath(rows[q][2]), int(rows[q][3]), int(o), int(s)))
+        closed = [(ids[f], int(file_size[f])) for f in range(len(ids) - 1 if r.open else len(ids))]
+        copies = {}
+        for name, found_here in zip(names, self._store_received(rows, ids, closed, block_file, digests, offsets,
+                                                                sizes, found)):
+            copies.setdefault(name, []).extend(found_here)
         return copies, r.consumed, ((ids[-1], r.end_offset) if r.open else None)
 
     def apply_block_data(self, digests, sizes, data_offsets, ok=None):
@@ -570,21 +616,25 @@ class Index:
         to keep for the next call.  Bytes the parser raises on, or another
         command, right after the messages raise wire.ProtocolError, and
         nothing is written."""
-        import torch
-
-        from . import wire
-        data = bytes(data)
-        dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        run = torch.frombuffer(bytearray(data), dtype=torch.uint8).to(dev) if data else \
-            torch.empty(0, dtype=torch.uint8, device=dev)
-        digests, sizes, offsets, ok, consumed, stop, _need = wire.receive_block_data_device(run, verify=verify)
-        if stop == wire.SF_WIRE_MALFORMED:
-            raise wire.ProtocolError("Malformed BLOCK_DATA run at byte %d" % consumed)
-        if stop == wire.SF_WIRE_OTHER:
-            raise wire.ProtocolError("Unexpected message in a BLOCK_DATA run (byte %d)" % consumed)
+        _run, digests, sizes, offsets, ok, consumed = self._parse_block_data(data, device, verify)
         writes, rejected = self.apply_block_data(digests.cpu().numpy(), sizes.cpu().numpy(), offsets.cpu().numpy(),
                                                  ok.cpu().numpy() if verify else None)
         return writes, rejected, consumed
+
+    @staticmethod
+    def _parse_block_data(data, device, verify: bool):
+        """The first step of ``receive_block_data`` and ``place_block_data``:
+        the received bytes uploaded, parsed and (``verify``) checked by
+        ``wire.receive_block_data_device``.  Returns (run, digests, sizes,
+        offsets, ok, consumed), all but the last on the device; raises
+        wire.ProtocolError for what may not follow the messages."""
+        from . import wire
+        from .device import upload
+        run = upload(bytes(data), device)
+        digests, sizes, offsets, ok, consumed, stop, _need = wire.receive_block_data_device(run, verify=verify)
+        _stop_error(stop, consumed, "BLOCK_DATA run", stop == wire.SF_WIRE_OTHER,
+                    "Unexpected message in a BLOCK_DATA run")
+        return run, digests, sizes, offsets, ok, consumed
 
     def missing_rows(self) -> List[Tuple[int, int, Optional[PurePath], int, int, HashDigest]]:
         """The rows ``list_missing_blocks`` reads (present = 0), in the same
@@ -597,12 +647,9 @@ class Index:
                  HashDigest.from_sql(r[5])) for r in rows]
 
     @staticmethod
-    def _digest_table(rows, dev):
-        import torch
-        raw = b"".join(r[5].bytes for r in rows)
-        if not raw:
-            return torch.empty((0, 20), dtype=torch.uint8, device=dev)
-        return torch.frombuffer(bytearray(raw), dtype=torch.uint8).reshape(-1, 20).to(dev)
+    def _digest_table(rows, device):
+        from .device import upload
+        return upload(b"".join(r[5].bytes for r in rows), device).reshape(len(rows), 20)
 
     def get_block_requests(self, device=None, distinct: bool = False):
         """The GET_BLOCK run the sink sends after the FILE_BLOCK runs
@@ -611,11 +658,8 @@ class Index:
         ``write_message("GetBlock", h)`` over ``list_missing_blocks()``, or
         with ``distinct`` one request per digest.  Returns the run (a
         ``wire.BlockDataRun``: ``bytes()``, ``to_fd(fd)``, ``close()``)."""
-        import torch
-
         from . import device as _device
-        dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        run, _n = _device.get_block_requests(self._digest_table(self.missing_rows(), dev), distinct=distinct)
+        run, _n = _device.get_block_requests(self._digest_table(self.missing_rows(), device), distinct=distinct)
         return run
 
     def place_block_data(self, data, images, device=None, verify: bool = True):
@@ -637,16 +681,8 @@ class Index:
         import torch
 
         from . import device as _device
-        from . import wire
-        data = bytes(data)
-        dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        run = torch.frombuffer(bytearray(data), dtype=torch.uint8).to(dev) if data else \
-            torch.empty(0, dtype=torch.uint8, device=dev)
-        digests, sizes, offsets, ok, consumed, stop, _need = wire.receive_block_data_device(run, verify=verify)
-        if stop == wire.SF_WIRE_MALFORMED:
-            raise wire.ProtocolError("Malformed BLOCK_DATA run at byte %d" % consumed)
-        if stop == wire.SF_WIRE_OTHER:
-            raise wire.ProtocolError("Unexpected message in a BLOCK_DATA run (byte %d)" % consumed)
+        run, digests, sizes, offsets, ok, consumed = self._parse_block_data(data, device, verify)
+        dev = run.device
         rows = self.missing_rows()
         n = len(rows)
         base, length = {}, {}
@@ -724,47 +760,42 @@ class Index:
         compared with the stored value as an instant (src/index.rs:183)."""
         self.begin()
         m = DateTimeUtc.coerce(modified)
-        ts = m.to_sql()
         cur = self.get_file(name)
+        if cur is not None and cur[1] == m:
+            return cur[0], True
         if cur is not None:
-            file_id, old_modified, _ = cur
-            if old_modified != m:
-                log.info("Resetting file %s, modified", name)
-                self.db.execute("DELETE FROM blocks WHERE file_id = ?;", (file_id,))
-                self.db.execute("UPDATE files SET modified = ?, size = NULL, blocks_hash = NULL, temporary = 0 "
-                                "WHERE file_id = ?;", (ts, file_id))
-                return file_id, False
-            return file_id, True
-        log.info("Inserting new file %s", name)
-        c = self.db.execute("INSERT INTO files(name, modified, temporary) VALUES(?, ?, 0);", (_name_str(name), ts))
-        return int(c.lastrowid), False
+            log.info("Resetting file %s, modified", name)
+        else:
+            log.info("Inserting new file %s", name)
+        return self._put_file(cur and cur[0], name, m, 0), False
+
+    def _put_file(self, file_id: Optional[int], name, modified: DateTimeUtc, temporary: int) -> int:
+        """The file row under add_file, add_file_overwrite and add_temp_file:
+        row ``file_id`` loses its blocks and is reset to ``modified`` and
+        ``temporary``; None: a new row for ``name``.  Returns the file_id."""
+        if file_id is not None:
+            self.db.execute("DELETE FROM blocks WHERE file_id = ?;", (file_id,))
+            self.db.execute("UPDATE files SET modified = ?, size = NULL, blocks_hash = NULL, temporary = ? "
+                            "WHERE file_id = ?;", (modified.to_sql(), temporary, file_id))
+            return file_id
+        c = self.db.execute("INSERT INTO files(name, modified, temporary) VALUES(?, ?, ?);",
+                            (_name_str(name), modified.to_sql(), temporary))
+        return int(c.lastrowid)
 
     def add_file_overwrite(self, name, modified) -> int:
         self.begin()
-        ts = DateTimeUtc.coerce(modified).to_sql()
+        m = DateTimeUtc.coerce(modified)
         cur = self.get_file(name)
-        if cur is not None:
-            file_id = cur[0]
-            self.db.execute("DELETE FROM blocks WHERE file_id = ?;", (file_id,))
-            self.db.execute("UPDATE files SET modified = ?, size = NULL, blocks_hash = NULL, temporary = 0 "
-                            "WHERE file_id = ?;", (ts, file_id))
-            return file_id
-        c = self.db.execute("INSERT INTO files(name, modified, temporary) VALUES(?, ?, 0);", (_name_str(name), ts))
-        return int(c.lastrowid)
+        return self._put_file(cur and cur[0], name, m, 0)
 
     def add_temp_file(self, name) -> int:
         self.begin()
-        ts = _now().to_sql()
+        now = _now()
         tname = _name_str(temp_name(name))
+        # the temp name is looked up among the files that are NOT temporary, as
+        # the reference does (src/index.rs:253-290)
         row = self.db.execute("SELECT file_id FROM files WHERE name = ? AND temporary = 0;", (tname,)).fetchone()
-        if row is not None:
-            file_id = int(row[0])
-            self.db.execute("DELETE FROM blocks WHERE file_id = ?;", (file_id,))
-            self.db.execute("UPDATE files SET modified = ?, size = NULL, blocks_hash = NULL, temporary = 1 "
-                            "WHERE file_id = ?;", (ts, file_id))
-            return file_id
-        c = self.db.execute("INSERT INTO files(name, modified, temporary) VALUES(?, ?, 1);", (tname, ts))
-        return int(c.lastrowid)
+        return self._put_file(row and int(row[0]), tname, now, 1)
 
     def remove_file(self, file_id: int) -> None:
         self.begin()
@@ -781,20 +812,17 @@ class Index:
     def add_block(self, hash: HashDigest, file_id: int, offset: int, size: int) -> None:
         """One row, present = 1 (src/index.rs:387-408)."""
         self.begin()
-        self.db.execute("INSERT INTO blocks(hash, file_id, offset, size, present) VALUES(?, ?, ?, ?, 1);",
-                        (hash.to_sql(), file_id, offset, size))
+        self.db.execute(INSERT_BLOCK, (hash.to_sql(), file_id, offset, size, 1))
 
     def add_blocks(self, file_id: int, rows: Sequence[Tuple[int, int, bytes]]) -> None:
         """add_block for a whole signature table in one executemany (the
         reference issues one un-prepared INSERT per block)."""
         self.begin()
-        self.db.executemany("INSERT INTO blocks(hash, file_id, offset, size, present) VALUES(?, ?, ?, ?, 1);",
-                            ((d.hex(), file_id, o, s) for o, s, d in rows))
+        self.db.executemany(INSERT_BLOCK, ((d.hex(), file_id, o, s, 1) for o, s, d in rows))
 
     def add_missing_block(self, hash: HashDigest, file_id: int, offset: int, size: int) -> None:
         self.begin()
-        self.db.execute("INSERT INTO blocks(hash, file_id, offset, size, present) VALUES(?, ?, ?, ?, 0);",
-                        (hash.to_sql(), file_id, offset, size))
+        self.db.execute(INSERT_BLOCK, (hash.to_sql(), file_id, offset, size, 0))
 
     def mark_block_present(self, file_id: int, hash: HashDigest, offset: int) -> None:
         self.begin()
@@ -839,29 +867,41 @@ class Index:
         fine as the filesystem's clock tick: a same-size write within the
         tick of the stamp is not seen, include/syncfast_amd.h.)"""
         self._need_chunker()
-        for attempt in range(CHANGED_RETRIES):
-            try:
-                self._index_file_once(path, name, force=attempt > 0)
-                return
-            except SfError as e:
-                if e.code != SF_EAGAIN:
-                    raise
+        self._index_file_retrying(path, name)
+
+    def _index_file_retrying(self, path, name, changed: bool = False) -> None:
+        """index_file's attempts: CHANGED_RETRIES, then the one-pass read.
+        ``changed``: the walk's own pass over the file (in a batch, or alone)
+        saw it change already.  Its row was added then, in walk order, so only
+        its blocks are indexed again; that pass is the one reported, and the
+        attempts here are all retries."""
+        for attempt in range(-1 if changed else 0, CHANGED_RETRIES):
+            if attempt >= 0:
+                try:
+                    self._index_file_once(path, name, force=changed or attempt > 0)
+                    return
+                except SfError as e:
+                    if e.code != SF_EAGAIN:
+                        raise
+            if attempt < 0 or not changed:
                 log.info("File %s changed while it was indexed, indexing it again", path)
-        log.info("File %s keeps changing: indexing the bytes of one read", path)
+        if not changed:
+            log.info("File %s keeps changing: indexing the bytes of one read", path)
         self._index_file_once(path, name, force=True, one_pass=True)
 
     def _index_file_once(self, path, name, force: bool, one_pass: bool = False, opened=None) -> None:
-        """One attempt of index_file; `opened`: the file already open (a FIFO
-        met by the walk is indexed from that open: a second open would wait
-        for another writer, and the first's data would be lost)."""
+        """One attempt of index_file; `opened`: the file already open, and the
+        caller's to close (a FIFO met by the walk is indexed from that open: a
+        second open would wait for another writer, and the first's data would
+        be lost)."""
         ch = self.chunker
         native = None  # (rows, blocks_hash) from a native route
-        with (open(path, "rb") if opened is None else opened) as f:  # File::open first: same error on a missing file
+        # File::open first: same error on a missing file
+        with (open(path, "rb") if opened is None else contextlib.nullcontext(opened)) as f:
             seekable = _seekable(f)
             stamp = host.file_stamp(f.fileno()) if seekable and not one_pass and \
                 (isinstance(ch, FixedChunker) or ch.stream) else None
-            mtime = DateTimeUtc.from_ns(stamp.mtime_sec * 10**9 + stamp.mtime_nsec) if stamp else _mtime(f)
-            file_id, up_to_date = self.add_file(name, mtime)
+            file_id, up_to_date = self.add_file(name, _stamp_mtime(stamp) if stamp else _mtime(f))
             if up_to_date:
                 if not force:
                     return
@@ -878,20 +918,16 @@ class Index:
                 else:  # a FIFO: read sequentially from this open, as File::open + read do
                     native = host.index_fd(f.fileno(), ch.block_size)
             elif isinstance(ch, NativeChunker) and seekable and not one_pass:
-                native = ch.index_fd(f.fileno(), ch.threads, stamp)  # cut + hash, one read
+                return self._index_fd_native(file_id, f, ch.threads, stamp)
             elif ch.stream and seekable and not one_pass:
-                sizes = [int(x) for x in ch.fn(f)]
-                if sum(sizes) != stamp.size and _stamp_moved(f.fileno(), stamp):
-                    raise SfError(SF_EAGAIN, f"index_file({os.fsdecode(path)})")  # written while chunked
-                sizes = _sizes_ok(sizes, stamp.size)
+                sizes = _cut_stamped(ch.fn, f, stamp)
+                if sizes is None:  # written while chunked
+                    raise SfError(SF_EAGAIN, f"index_file({os.fsdecode(path)})")
                 native = host.index_fd_blocks(f.fileno(), _offsets(sizes), np.asarray(sizes, np.uint32), stamp)
             else:
                 rows = signatures_of_bytes(f.read(), ch)
         if native is not None:
-            rows_np, bh = native
-            self._insert_rows(file_id, rows_np)
-            self.db.execute("UPDATE files SET blocks_hash = ? WHERE file_id = ?;", (bh.hex(), file_id))
-            return
+            return self._store_rows(file_id, *native)
         if log.isEnabledFor(logging.DEBUG):
             for o, sz, d in rows:
                 log.debug("Adding block, offset=%d, size=%d, sha1=%s", o, sz, d.hex())
@@ -899,9 +935,11 @@ class Index:
         bh = self.compute_blocks_hash(file_id)
         self.db.execute("UPDATE files SET blocks_hash = ? WHERE file_id = ?;", (bh.to_sql(), file_id))
 
-    def _insert_rows(self, file_id: int, rows, a: int = 0, b: Optional[int] = None) -> None:
-        """add_block for rows[a:b] of a native signature table: the hash column
-        hex-encoded once (HashDigest ToSql, src/lib.rs:78-90), one executemany."""
+    def _store_rows(self, file_id: int, rows, blocks_hash, a: int = 0, b: Optional[int] = None) -> None:
+        """A file's native result, stored: add_block for rows[a:b] of a native
+        signature table -- the hash column hex-encoded once (HashDigest ToSql,
+        src/lib.rs:78-90), one executemany -- and the file's ``blocks_hash``
+        (bytes, or 20 uint8)."""
         self.begin()
         b = rows.shape[0] if b is None else b
         hx = rows["sha1"][a:b].tobytes().hex()
@@ -909,8 +947,15 @@ class Index:
         if log.isEnabledFor(logging.DEBUG):
             for i in range(b - a):
                 log.debug("Adding block, offset=%d, size=%d, sha1=%s", offs[i], sizes[i], hx[40 * i:40 * i + 40])
-        self.db.executemany("INSERT INTO blocks(hash, file_id, offset, size, present) VALUES(?, ?, ?, ?, 1);",
-                            ((hx[40 * i:40 * i + 40], file_id, offs[i], sizes[i]) for i in range(b - a)))
+        self.db.executemany(INSERT_BLOCK, zip((hx[i:i + 40] for i in range(0, len(hx), 40)), itertools.repeat(file_id),
+                                              offs, sizes, itertools.repeat(1)))
+        self.db.execute("UPDATE files SET blocks_hash = ? WHERE file_id = ?;", (bytes(blocks_hash).hex(), file_id))
+
+    def _index_fd_native(self, file_id: int, f, threads: int, stamp) -> None:
+        """The open, stamped regular file ``f``, already through the mtime gate
+        as ``file_id``, cut and hashed in one call by the NativeChunker on
+        ``threads`` threads (``index_fd``: one read), and stored."""
+        self._store_rows(file_id, *self.chunker.index_fd(f.fileno(), threads, stamp))
 
     def index_path(self, path, batch_bytes: int = 256 << 20, chunk_threads: int = 0,
                    large_file_bytes: int = LARGE_FILE_BYTES) -> None:
@@ -981,19 +1026,15 @@ class Index:
                 if not up_to_date and not _seekable(f):
                     # a FIFO in the tree: read it from this open (a second
                     # open would wait for another writer); rows like index_file
-                    rows_np, bh = host.index_fd(f.fileno(), bs)
-                    self._insert_rows(file_id, rows_np)
-                    self.db.execute("UPDATE files SET blocks_hash = ? WHERE file_id = ?;", (bh.hex(), file_id))
+                    self._store_rows(file_id, *host.index_fd(f.fileno(), bs))
                     continue
             if not up_to_date:
                 pending.append((file_id, p))
         if not pending:
             return
         rows, first, fh = host.index_files([p for _f, p in pending], bs, stage_bytes=batch_bytes)
-        fhx = fh.tobytes().hex()
         for k, (file_id, _p) in enumerate(pending):
-            self._insert_rows(file_id, rows, int(first[k]), int(first[k + 1]))
-            self.db.execute("UPDATE files SET blocks_hash = ? WHERE file_id = ?;", (fhx[40 * k:40 * k + 40], file_id))
+            self._store_rows(file_id, rows, fh[k], int(first[k]), int(first[k + 1]))
 
     def _index_batched_fds(self, todo, batch_bytes: int, chunk_threads: int,
                            large_file_bytes: int = LARGE_FILE_BYTES) -> None:
@@ -1022,115 +1063,73 @@ class Index:
         threads = chunk_threads if chunk_threads > 0 else min(16, os.cpu_count() or 1)
         soft = resource.getrlimit(resource.RLIMIT_NOFILE)[0]
         max_files = max(16, min(4096, (soft if soft > 0 else 1024) // 4))
+        native = isinstance(ch, NativeChunker)
 
-        def cut(f, stamp):
-            sizes = [int(x) for x in ch.fn(f)]
-            if sum(sizes) != stamp.size and _stamp_moved(f.fileno(), stamp):
-                return None  # written while it was cut
-            return _sizes_ok(sizes, stamp.size)
-
-        def finish(batch, futs):
-            try:
-                cuts = [fu.result() for fu in futs]
-                keep = [k for k, c in enumerate(cuts) if c is not None]
-                lists = [(_offsets(cuts[k]), np.asarray(cuts[k], np.uint32)) for k in keep]
-                res = host.index_fds_blocks([batch[k][3].fileno() for k in keep], lists,
-                                            [batch[k][4] for k in keep], stage_bytes=batch_bytes) if keep else None
-            finally:
-                for _fid, _p, _rel, f, _st in batch:
-                    f.close()
+        def finish(batch):
+            """Hash the cut files of `batch` in one call, close them, store them."""
+            entries = batch.entries
+            if not entries:
+                return
+            cuts = [e[5].result() for e in entries]
+            keep = [k for k, c in enumerate(cuts) if c is not None]
+            lists = [(_offsets(cuts[k]), np.asarray(cuts[k], np.uint32)) for k in keep]
+            res = host.index_fds_blocks([entries[k][3].fileno() for k in keep], lists,
+                                        [entries[k][4] for k in keep], stage_bytes=batch_bytes) if keep else None
+            batch.close()  # cut and hashed: nothing reads its descriptors any more
             pos = {k: j for j, k in enumerate(keep)}
-            for k, (fid, p, rel, _f, _st) in enumerate(batch):
+            for k, (fid, p, rel, _f, _st, _fut) in enumerate(entries):
                 j = pos.get(k)
                 if j is not None and res[3][j] == 0:
                     rows, first, hashes, _status = res
-                    self._insert_rows(fid, rows, int(first[j]), int(first[j + 1]))
-                    self.db.execute("UPDATE files SET blocks_hash = ? WHERE file_id = ?;",
-                                    (bytes(hashes[j]).hex(), fid))
+                    self._store_rows(fid, rows, hashes[j], int(first[j]), int(first[j + 1]))
                     continue
                 code = SF_EAGAIN if j is None else int(res[3][j])
                 if code != SF_EAGAIN:
                     raise SfError(code, f"index_file({os.fsdecode(p)})")
-                log.info("File %s changed while it was indexed, indexing it again", p)
                 self.db.execute("DELETE FROM blocks WHERE file_id = ?;", (fid,))
-                self._index_file_changed(p, rel)
+                self._index_file_retrying(p, rel, changed=True)
 
-        prev = None
-        batch, futs, nbytes = [], [], 0
-        native = isinstance(ch, NativeChunker)
-
-        def drain():
-            """Store every batch before the file about to be indexed alone."""
-            nonlocal prev, batch, futs, nbytes
-            if prev is not None:
-                p_, prev = prev, None
-                finish(*p_)
-            if batch:
-                b_, f_ = batch, futs
-                batch, futs, nbytes = [], [], 0
-                finish(b_, f_)
-
-        pool = ThreadPoolExecutor(max_workers=threads)
-        try:
+        # Two batches: `cutting` is filled while the pool cuts its files,
+        # `hashing` is the full one before it.  They own their open files: a
+        # batch that was hashed is closed there (finish); leaving this block
+        # closes what an exception left in them or never submitted -- after the
+        # pool, which is entered last, has shut down, so no chunker is still
+        # reading a descriptor that is being closed.
+        with _FdBatch() as cutting, _FdBatch() as hashing, ThreadPoolExecutor(max_workers=threads) as pool:
             for p, rel in todo:
-                f = open(p, "rb")  # File::open first: same error on a missing file
-                try:
-                    if not _seekable(f):  # a FIFO: read from this open, sequentially, in its place
-                        drain()
-                        self._index_file_once(p, rel, force=False, opened=f)  # closes f
-                        continue
-                    stamp = host.file_stamp(f.fileno())
-                    file_id, up_to_date = self.add_file(
-                        rel, DateTimeUtc.from_ns(stamp.mtime_sec * 10**9 + stamp.mtime_nsec))
-                    if not up_to_date and native and stamp.size >= large_file_bytes > 0:
-                        drain()
-                        try:  # cut on the chunker's threads + hashed, one read of this open
-                            rows_np, bh = ch.index_fd(f.fileno(), ch.threads or threads, stamp)
-                        except SfError as e:
-                            if e.code != SF_EAGAIN:
-                                raise
-                            log.info("File %s changed while it was indexed, indexing it again", p)
-                            f.close()
-                            self._index_file_changed(p, rel)
+                changed = False
+                with contextlib.ExitStack() as mine:  # the open file is this step's until a batch takes it
+                    f = mine.enter_context(open(p, "rb"))  # File::open first: same error on a missing file
+                    fifo = not _seekable(f)
+                    if not fifo:
+                        stamp = host.file_stamp(f.fileno())
+                        file_id, up_to_date = self.add_file(rel, _stamp_mtime(stamp))
+                        if up_to_date:
                             continue
-                        self._insert_rows(file_id, rows_np)
-                        self.db.execute("UPDATE files SET blocks_hash = ? WHERE file_id = ?;", (bh.hex(), file_id))
-                        f.close()
-                        continue
-                except BaseException:
-                    f.close()
-                    raise
-                if up_to_date:
-                    f.close()
-                    continue
-                batch.append((file_id, p, rel, f, stamp))
-                futs.append(pool.submit(cut, f, stamp))
-                nbytes += stamp.size
-                if nbytes >= batch_bytes or len(batch) >= max_files:
-                    if prev is not None:
-                        finish(*prev)  # hashed while the pool cuts this batch
-                    prev, batch, futs, nbytes = (batch, futs), [], [], 0
-            if prev is not None:
-                finish(*prev)
-            if batch:
-                finish(batch, futs)
-        finally:
-            pool.shutdown(wait=True)  # no chunker still reading a descriptor closed below
-            for b in ([prev[0]] if prev is not None else []) + [batch]:
-                for _fid, _p, _rel, f, _st in b:
-                    f.close()  # idempotent: the finished batches' are closed already
-
-    def _index_file_changed(self, path, name) -> None:
-        """index_file of a file whose first pass saw it change: its row was
-        added in walk order already, so only its blocks are indexed again."""
-        for attempt in range(CHANGED_RETRIES):
-            try:
-                self._index_file_once(path, name, force=True)
-                return
-            except SfError as e:
-                if e.code != SF_EAGAIN:
-                    raise
-        self._index_file_once(path, name, force=True, one_pass=True)
+                    if fifo or (native and stamp.size >= large_file_bytes > 0):
+                        # indexed alone, in its walk position: every batch before it is stored first
+                        finish(hashing)
+                        finish(cutting)
+                        try:
+                            if fifo:  # read from this open, sequentially
+                                self._index_file_once(p, rel, force=False, opened=f)
+                            else:  # cut on the chunker's threads + hashed, one read of this open
+                                self._index_fd_native(file_id, f, ch.threads or threads, stamp)
+                        except SfError as e:
+                            if fifo or e.code != SF_EAGAIN:
+                                raise
+                            changed = True
+                    else:
+                        cutting.enter_context(mine.pop_all())
+                        cutting.entries.append((file_id, p, rel, f, stamp, pool.submit(_cut_stamped, ch.fn, f, stamp)))
+                        cutting.nbytes += stamp.size
+                if changed:
+                    self._index_file_retrying(p, rel, changed=True)
+                elif cutting.nbytes >= batch_bytes or len(cutting.entries) >= max_files:
+                    finish(hashing)  # hashed while the pool cuts the batch that is now full
+                    cutting, hashing = hashing, cutting
+            finish(hashing)
+            finish(cutting)
 
     def _index_batched_boundaries(self, todo, batch_bytes: int) -> None:
         """The default (content-defined) mode over many files: each file is
@@ -1164,9 +1163,7 @@ class Index:
                 mine = rows[k:k + len(sz)].copy()
                 k += len(sz)
                 mine["offset"] -= np.uint64(base)
-                self._insert_rows(fid, mine)
-                bh = host.blocks_hash(np.ascontiguousarray(mine["sha1"]))
-                self.db.execute("UPDATE files SET blocks_hash = ? WHERE file_id = ?;", (bh.hex(), fid))
+                self._store_rows(fid, mine, host.blocks_hash(np.ascontiguousarray(mine["sha1"])))
             batch, parts, nbytes = [], [], 0
 
         for p, rel in todo:

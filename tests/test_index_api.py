@@ -6,6 +6,7 @@ SQLite row semantics of src/index.rs; GPU tests mirror the index KAT
 with fixed-size blocks against the oracle."""
 import datetime as dt
 import hashlib
+import itertools
 import os
 from pathlib import PurePath
 
@@ -539,6 +540,46 @@ def test_index_path_stream_chunker_many_files(tmp_path, monkeypatch, threads, ba
     before = idx.db.execute("SELECT COUNT(*) FROM blocks").fetchone()[0]
     idx.index_path(root, batch_bytes=batch_bytes, chunk_threads=threads)  # mtimes unchanged: nothing again
     assert idx.db.execute("SELECT COUNT(*) FROM blocks").fetchone()[0] == before
+
+
+class _Planted(Exception):
+    pass
+
+
+@pytest.mark.parametrize("case", ["completes", "chunker raises", "index_fds_blocks raises"])
+@pytest.mark.parametrize("batch_bytes", [20_000, 1 << 30])
+def test_index_path_stream_chunker_leaves_no_descriptor_open(tmp_path, monkeypatch, batch_bytes, case):
+    """The walk's open files are all closed when index_path returns: after a
+    complete walk, after the chunker raised on its third file and after the
+    many-file call raised -- and the two failures surface unchanged."""
+    from syncfast_amd import host
+    _oracle_device_calls(monkeypatch)
+    root = tmp_path / "tree"
+    _tree(root, 4350)
+    seen, order = [], itertools.count(1)
+
+    def chunker(f):
+        seen.append(f)
+        if next(order) == 3 and case == "chunker raises":  # next(): one thread of the pool gets the 3
+            raise _Planted("chunker")
+        return _stream_toy_cdc(f)
+
+    def fds_raise(fds, lists, stamps=None, stage_bytes=0):
+        raise _Planted("index_fds_blocks")
+
+    if case == "index_fds_blocks raises":
+        monkeypatch.setattr(host, "index_fds_blocks", fds_raise)
+    idx = Index.open_in_memory(chunker=BoundaryChunker(chunker, stream=True))
+    before = len(os.listdir("/proc/self/fd"))
+    if case == "completes":
+        idx.index_path(root, batch_bytes=batch_bytes, chunk_threads=2)
+        assert len(idx.list_files()) == 5
+    else:
+        with pytest.raises(_Planted, match=case.split()[0]) as e:
+            idx.index_path(root, batch_bytes=batch_bytes, chunk_threads=2)
+        assert type(e.value) is _Planted and e.value.args == (case.split()[0],)
+    assert len(seen) >= 3 and all(f.closed for f in seen)
+    assert len(os.listdir("/proc/self/fd")) == before
 
 
 def test_index_path_stream_chunker_file_changed_is_reindexed(tmp_path, monkeypatch):
