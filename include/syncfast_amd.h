@@ -541,6 +541,60 @@ int sf_wire_run_to_fd(const sf_wire_run *run, int fd, uint64_t *n_written);
 
 int sf_wire_run_free(sf_wire_run *run, void *stream);
 
+/* ------------------------- answering GET_FILE requests, from the device ---- */
+
+/* The source's answer to a list of GET_FILE requests.  The destination sends
+ * every GET_FILE at once, and FsSource answers them back to back: for each
+ * file "FILE_START\n" + name + "\n", one FILE_BLOCK per row of
+ * list_file_blocks, "FILE_END\n" (src/sync/fs.rs:177-231, written by
+ * src/sync/ssh/proto.rs:157-169).  Here the whole answer -- the stream
+ * sf_receive_files_device takes -- is built in HBM in one call.
+ *
+ * Blocks: d_digests + 20 * i and d_sizes[i], any uint32, for all files
+ * together in answer order.  Files: d_file_first[0, n_files] is the CSR into
+ * them (file f owns blocks [d_file_first[f], d_file_first[f + 1]); an empty
+ * file owns none) and d_name_at[0, n_files] the CSR into the packed name
+ * bytes d_names[0, d_name_at[n_files]) (any address; may be NULL when every
+ * name is empty).  With E the inclusive end offsets of the FILE_BLOCK
+ * messages alone (33 + digits(size) bytes each) and Bex(i) = i ? E[i - 1] : 0:
+ *   FILE_START of file f   at Bex(first[f]) + name_at[f] + 21 f
+ *   FILE_BLOCK i of file f at Bex(i) + name_at[f + 1] + 21 f + 12
+ *   FILE_END of file f     at Bex(first[f + 1]) + name_at[f + 1] + 21 f + 12
+ *   the run's length       = Bex(n_blocks) + name_at[n_files] + 21 n_files
+ * byte for byte what write_message gives, n_blocks + 2 n_files messages.
+ *
+ * File f is refused when its entries do not hold: first[0] == 0, first[f] <=
+ * first[f + 1], first[n_files] == n_blocks, name_at[0] == 0, name_at[f] <=
+ * name_at[f + 1] <= name_at[n_files], and a name of at most 100 bytes with no
+ * '\n' in it -- the names the protocol can carry (read_line(FILENAME_MAX),
+ * proto.rs:271-290); no other name can have arrived in a GET_FILE, and the
+ * receiver could not parse one.  Then the call returns SF_EINVAL with
+ * *bad_file = the first such file and *run = NULL, and keeps nothing
+ * allocated; no byte outside the arrays as described is loaded.  *bad_file =
+ * UINT64_MAX in every other case.
+ *
+ * *run is the handle above (sf_wire_run_info, _read, _to_fd, _free).  The
+ * block lengths are scanned as for sf_wire_blocks_device, one lane per file
+ * tests its entries and its name (the first failing file is an atomic
+ * minimum, one atomic per wave), the scan's total, name_at[n_files] and that
+ * word come back in one 24-byte copy (the call blocks there, once), then one
+ * lane per file writes its FILE_START and FILE_END and one lane per block
+ * finds its file by an upper-bound binary search of d_file_first and writes
+ * its FILE_BLOCK, all with byte stores (sf_send_files.hip).
+ * No array is written; all may still be in production on `stream`.  Scratch:
+ * 16 n_blocks bytes plus the scan's.  n_files == 0 with n_blocks == 0 gives an
+ * empty run, launches nothing and needs no device.  SF_EINVAL, before any
+ * device call, for a NULL run or bad_file, for n_blocks + 2 n_files > 2^32,
+ * for blocks without a file, for a NULL d_file_first or d_name_at with
+ * n_files > 0, for a NULL d_digests or d_sizes with n_blocks > 0, for a
+ * d_digests or d_sizes that is not 4-B aligned and for a d_file_first or
+ * d_name_at that is not 8-B aligned. */
+int sf_wire_files_device(const void *d_digests /* n_blocks x 20 B: 4-B aligned */,
+                         const uint32_t *d_sizes, uint64_t n_blocks,
+                         const uint64_t *d_file_first /* n_files + 1 */, const void *d_names,
+                         const uint64_t *d_name_at /* n_files + 1 */, uint64_t n_files,
+                         sf_wire_run **run, uint64_t *bad_file, void *stream);
+
 /* ----------------------- the destination's missing blocks, on the device ---- */
 
 /* The two steps between the runs.  After the FILE_BLOCK runs the sink lists

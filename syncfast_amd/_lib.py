@@ -129,6 +129,7 @@ def _table():
         "sf_wire_run_read": (i32, [vp, u64, vp, u64]),
         "sf_wire_run_to_fd": (i32, [vp, i32, pu64]),
         "sf_wire_run_free": (i32, [vp, vp]),
+        "sf_wire_files_device": (i32, [vp, vp, u64, vp, vp, vp, u64, P(vp), pu64, vp]),
         "sf_wire_get_blocks_device": (i32, [vp, vp, vp, u64, i32, P(vp), pu64, vp]),
         "sf_place_block_data_device": (i32, [vp, vp, vp, vp, u64, vp, vp, vp, vp, u64, vp, vp, vp, vp, vp, u64, vp,
                                             pu64, pu64, pu64, vp]),

@@ -45,6 +45,10 @@
 //   sf_send.hip   BLOCK_DATA runs built on the device, and a GET_BLOCK run
 //                 answered in one call (its own kernels; the rules are
 //                 sf_wire_data.hpp; the payloads go through sf_copy.hip).
+//   sf_send_files.hip  the source's answer to a list of GET_FILE requests --
+//                 every file's FILE_START, FILE_BLOCKs and FILE_END -- built
+//                 in one call (its own kernels; the rules are
+//                 sf_wire_send_files.hpp; the block scan is sf_wire.hip's).
 //   sf_want.hip   the destination's GET_BLOCK run built from its missing rows,
 //                 and a parsed BLOCK_DATA run joined against them into a copy
 //                 list (its own kernels; the rules are sf_want_plan.hpp; the

@@ -707,6 +707,59 @@ class Index:
             if verify else []
         return int(job_rows.numel()), rejected, consumed, n_left
 
+    def serve_get_files(self, names, device=None):
+        """The source's ``Respond`` state for a list of requested names
+        (src/sync/fs.rs:177-231): each name -- the bytes of a GET_FILE -- is
+        decoded as UTF-8 (a bad encoding raises wire.ProtocolError,
+        Error::BadFilenameEncoding) and resolved with ``get_file``, and its
+        answer is FILE_START with the name, one FILE_BLOCK per row of
+        ``list_file_blocks(file_id)`` in exactly that order, and FILE_END.
+
+        Returns (run, n_answered).  Answering stops before the first name the
+        index does not hold (a temporary file's name is not held): the
+        reference answers those before it and then fails with "Requested file
+        is unknown", so the caller sends the run and raises that when
+        ``n_answered < len(names)``, as ``BlockSet.serve`` documents for
+        digests.  ``device=None`` is the definition, the ``write_message``
+        loop, and ``run`` is bytes.  With a device the rows of all answered
+        files go up in one upload and ONE ``wire.files_device`` call
+        (sf_wire_files_device) builds the answer in HBM: ``run`` is a
+        ``wire.FilesRun`` (``bytes()``, ``to_fd(fd)``, ``receive``,
+        ``close()``).  Parsing the received GET_FILE run stays with
+        ``wire.Parser``; the name lookup is SQLite's, on the host."""
+        from . import wire
+        files = []  # (name bytes, [(hash, offset, size)])
+        for name in names:
+            raw = bytes(name)
+            try:
+                text = raw.decode("utf-8")
+            except UnicodeDecodeError:
+                raise wire.ProtocolError("Bad filename encoding") from None
+            found = self.get_file(PurePath(text))
+            if found is None:
+                break
+            files.append((raw, self.list_file_blocks(found[0])))
+        if device is None:
+            return b"".join(wire.write_message("FileStart", raw)
+                            + b"".join(wire.write_message("FileBlock", h, size) for h, _offset, size in blocks)
+                            + wire.write_message("FileEnd") for raw, blocks in files), len(files)
+        import torch
+
+        from .device import device_of, upload
+        dev = device_of(device)
+        rows = [b for _raw, blocks in files for b in blocks]
+        # one buffer, widest elements first so that every part starts on its own grid
+        parts = [np.cumsum([0] + [len(blocks) for _raw, blocks in files], dtype=np.int64).tobytes(),
+                 np.cumsum([0] + [len(raw) for raw, _blocks in files], dtype=np.int64).tobytes(),
+                 np.fromiter((size for _h, _offset, size in rows), np.uint32, len(rows)).tobytes(),
+                 b"".join(h.bytes for h, _offset, _size in rows), b"".join(raw for raw, _blocks in files)]
+        buf = upload(b"".join(parts), dev)
+        at = np.cumsum([0] + [len(p) for p in parts]).tolist()
+        first, name_at, sizes, digests, packed = (buf[a:b] for a, b in zip(at, at[1:]))
+        run = wire.files_device(digests.reshape(len(rows), 20), sizes.view(torch.int32), first.view(torch.int64),
+                                packed, name_at.view(torch.int64))
+        return run, len(files)
+
     def get_file(self, name) -> Optional[Tuple[int, DateTimeUtc, Optional[HashDigest]]]:
         row = self.db.execute(
             "SELECT file_id, modified, blocks_hash FROM files WHERE name = ? AND temporary = 0;",

@@ -11,7 +11,8 @@ the incremental framing parser a destination runs over the same bytes.
 ``block_data_device`` builds the source's BLOCK_DATA run on the GPU
 (sf_wire_block_data_device) as a ``BlockDataRun``, which
 ``device.BlockSet.serve`` also returns for a received run of GET_BLOCK
-requests."""
+requests.  ``files_device`` builds the source's whole answer to a list of
+GET_FILE requests (sf_wire_files_device) as a ``FilesRun``."""
 from __future__ import annotations
 
 import ctypes
@@ -407,6 +408,64 @@ def block_data_device(src, digests, src_offsets, sizes, stream=None) -> BlockDat
                                               dev._ptr(src_offsets, n), dev._ptr(sizes, n), n, ctypes.byref(h),
                                               _stream(torch, src)), "sf_wire_block_data_device")
     return BlockDataRun(h, src.device, stream)
+
+
+class FilesRun(BlockDataRun):
+    """A whole GetFiles answer built in HBM (``files_device``,
+    ``Index.serve_get_files``): FILE_START, FILE_BLOCKs and FILE_END of file
+    after file in one library-owned run.  ``BlockDataRun`` in everything but
+    what ``receive`` does with it."""
+
+    def receive(self, block_set=None, open: bool = False, base_offset: int = 0):
+        """The run handed straight to ``device.BlockSet.receive_files``
+        (sf_receive_files_device) -- the destination's half of the exchange --
+        and its ``FilesReceived``.  ``block_set`` None: a set of no rows, so
+        every block comes back not found (rows -1)."""
+        from . import device
+        import torch
+        run = self.tensor()
+        if block_set is not None:
+            return block_set.receive_files(run, open=open, base_offset=base_offset)
+        with device.BlockSet(torch.empty((0, 20), dtype=torch.uint8, device=self.device), stream=self.stream) as none:
+            return none.receive_files(run, open=open, base_offset=base_offset)
+
+
+def files_device(digests, sizes, file_first, names, name_at, stream=None) -> FilesRun:
+    """The source's answer to a list of GET_FILE requests, built on the device
+    in one call (sf_wire_files_device): for file f ``write_message("FileStart",
+    name)``, one ``write_message("FileBlock", digest, size)`` per block and
+    ``write_message("FileEnd")``, file after file, byte for byte.  ``digests``
+    uint8[n, 20] and ``sizes`` int32/uint32[n] (bit pattern taken as uint32)
+    hold the blocks of all files in answer order; ``file_first`` int64[m + 1]
+    is the CSR into them (file f owns blocks ``file_first[f]:file_first[f +
+    1]``), ``names`` uint8 the packed name bytes and ``name_at`` int64[m + 1]
+    the CSR into those.  All are HBM tensors on one device.  A broken CSR, or a
+    name the protocol cannot carry (over 100 bytes, or holding a newline),
+    raises ValueError naming the first such file, and nothing is built.
+    Blocking, for one read-back."""
+    torch, dev = _device(digests, "digests")
+    d = digests.device
+    if digests.dim() != 2 or digests.shape[1] != 20:
+        raise ValueError("digests must be uint8[n, 20]")
+    n = digests.shape[0]
+    _check_sizes(torch, sizes, digests)
+    dev._require_device(file_first, "file_first", torch.int64, d)
+    dev._require_device(names, "names", torch.uint8, d)
+    dev._require_device(name_at, "name_at", torch.int64, d)
+    m = file_first.numel() - 1
+    if m < 0 or name_at.numel() != m + 1 or file_first.dim() != 1 or name_at.dim() != 1 or names.dim() != 1:
+        raise ValueError("file_first and name_at must be flat and hold one entry per file and one more")
+    h, bad = ctypes.c_void_p(), ctypes.c_uint64(0)
+    with dev._on(d, stream):
+        sizes = sizes.contiguous()
+        rc = lib().sf_wire_files_device(dev._ptr(digests, n), dev._ptr(sizes, n), n, file_first.data_ptr(),
+                                        dev._ptr(names), name_at.data_ptr(), m, ctypes.byref(h), ctypes.byref(bad),
+                                        _stream(torch, digests))
+    if rc != SF_OK and bad.value != (1 << 64) - 1:
+        raise ValueError(f"file {bad.value}: its block or name entries do not hold, or its name is over "
+                         f"{FILENAME_MAX} bytes or holds a newline")
+    check(rc, "sf_wire_files_device")
+    return FilesRun(h, d, stream)
 
 
 def blocks_to_fd(digests, sizes, fd: int, stream=None) -> int:
