@@ -276,8 +276,10 @@ enum {
     SF_WIRE_OTHER = 2,      /* a complete command line of another message (FILE_END, ...):
                                the caller's parser takes over there */
     SF_WIRE_MALFORMED = 3,  /* the reference parser would raise there */
-    SF_WIRE_UNEXPECTED = 4  /* sf_receive_files_device only: a whole, valid FILE_START, FILE_BLOCK or
+    SF_WIRE_UNEXPECTED = 4, /* sf_receive_files_device only: a whole, valid FILE_START, FILE_BLOCK or
                                FILE_END that the sink's state does not take there */
+    SF_WIRE_END_FILES = 5   /* sf_receive_file_entries_device only: "END_FILES\n" stood after the last
+                               entry and is counted in *consumed */
 };
 
 /* The inverse of sf_wire_blocks_device: the longest prefix of whole FILE_BLOCK
@@ -594,6 +596,146 @@ int sf_wire_files_device(const void *d_digests /* n_blocks x 20 B: 4-B aligned *
                          const uint64_t *d_file_first /* n_files + 1 */, const void *d_names,
                          const uint64_t *d_name_at /* n_files + 1 */, uint64_t n_files,
                          sf_wire_run **run, uint64_t *bad_file, void *stream);
+
+/* ------------------------------ exchanging the files list, on the device ---- */
+
+/* The first phase of a sync (src/sync/fs.rs).  The source sends its files
+ * list, one "FILE_ENTRY\n" + name + "\n" + size + "\n" + 20 B blocks_hash +
+ * "\n" per file and "END_FILES\n" (fs.rs:133-164, proto.rs:142-151); the
+ * destination looks every name up in its index, compares the announced
+ * blocks_hash with the recorded one and asks for the files that differ or are
+ * unknown, one "GET_FILE\n" + name + "\n" each (fs.rs:378-446, proto.rs:152-156)
+ * -- the requests sf_wire_files_device answers.  Here: the lookup by name for
+ * a whole list (a name set), the list built in one call, the list received in
+ * one call, and the request run built in one call (sf_names.hip,
+ * sf_send_entries.hip, sf_recv_entries.hip). */
+
+/* Index::get_file for a whole list at once, the sibling of the block set:
+ * the destination's names as an open-addressing table in HBM.  Row r's name is
+ * d_names[d_name_at[r], d_name_at[r + 1]): packed bytes at any address and
+ * their CSR (n_rows + 1 entries, 8-B aligned), rows in file_id order; a name
+ * may have any length, 0 and more than 100 included.  d_present (optional, one
+ * byte per row, the mirror of temporary = 0): a row with 0 is not in the set.
+ * Both arrays must stay as they are while the set is used.  A CSR that does
+ * not hold (d_name_at[0] != 0, an entry above its successor or above the last
+ * one) gives SF_EINVAL with *bad_row = the first such row, and nothing is kept
+ * allocated; *bad_row = UINT64_MAX in every other case.  One lane per row
+ * tests its entries and inserts its row id with one atomic compare-and-swap per
+ * probe; the first bad row comes back (the call blocks there, once).  Memory:
+ * 16 to 32 bytes per row from the library's stream-ordered pool, until
+ * sf_name_set_free (stream-ordered).  n_rows == 0 gives a set that answers -1
+ * everywhere, launches nothing and needs no device.  SF_EINVAL, before any
+ * device call, for a NULL out or bad_row, n_rows > 2^31, a NULL d_name_at with
+ * n_rows > 0 or one that is not 8-B aligned. */
+typedef struct sf_name_set sf_name_set;
+int sf_name_set_build(const void *d_names, const uint64_t *d_name_at /* n_rows + 1 */,
+                      const uint8_t *d_present /* may be NULL */, uint64_t n_rows, sf_name_set **out,
+                      uint64_t *bad_row, void *stream);
+
+/* Query i is the d_len[i] bytes at d_bytes + d_at[i] -- spans anywhere in
+ * d_bytes[0, n_bytes), no alignment: the shape sf_receive_files_device and
+ * sf_receive_file_entries_device write.  d_rows[i] = the lowest present row
+ * whose name has the same length and the same bytes, or -1: what get_file's
+ * rows.next() gives through idx_files_name (the schema has no UNIQUE on name).
+ * A span that leaves d_bytes[0, n_bytes) is not read and gives -1.  The set is
+ * only read; asynchronous on `stream`.  SF_EINVAL, before any device call,
+ * for a NULL set, a NULL array with n_query > 0, a NULL d_bytes with
+ * n_bytes > 0, a d_at or d_rows that is not 8-B aligned or a d_len that is not
+ * 4-B aligned. */
+int sf_name_set_lookup(const sf_name_set *set, const void *d_bytes, uint64_t n_bytes, const uint64_t *d_at,
+                       const uint32_t *d_len, uint64_t n_query, int64_t *d_rows, void *stream);
+int sf_name_set_free(sf_name_set *set, void *stream);
+
+/* The source's ListFiles state in one call: for file f write_message's
+ * FILE_ENTRY of its name d_names[d_name_at[f], d_name_at[f + 1]) (packed bytes
+ * at any address, CSR of n_files + 1 entries), d_sizes[f] and the 20 bytes at
+ * d_hashes + 20 f, file after file, and "END_FILES\n" behind them when
+ * end_files != 0: 34 + name + digits(size) bytes per entry, byte for byte what
+ * the reference writes.  *run is the handle above (sf_wire_run_info, _read,
+ * _to_fd, _free).
+ * File f is refused when its CSR entries do not hold (as for
+ * sf_wire_files_device), when its name is over 100 bytes or holds '\n', or
+ * when its size is 10^15 or more (a field of 16 digits, which the receiver's
+ * read_line(SIZE_MAX) cannot take).  The reference would send such an entry,
+ * and its peer would raise in the middle of the list.  Then the call returns
+ * SF_EINVAL with *bad_file = the first such file and *run = NULL and keeps
+ * nothing allocated; *bad_file = UINT64_MAX in every other case.
+ * One lane per file tests it and gives its entry's length, a scan places the
+ * entries, the first bad file and the total come back (the call blocks there,
+ * once), then one lane per entry writes it with byte stores.  Scratch: 12
+ * n_files bytes plus the scan's.  n_files == 0 gives an empty run, launches
+ * nothing and needs no device -- or, with end_files, the 10-byte run.
+ * SF_EINVAL, before any device call, for a NULL run or bad_file, n_files >
+ * 2^31, a NULL d_name_at, d_sizes or d_hashes with n_files > 0, a d_name_at or
+ * d_sizes that is not 8-B aligned or a d_hashes that is not 4-B aligned. */
+int sf_wire_file_entries_device(const void *d_names, const uint64_t *d_name_at /* n_files + 1 */,
+                                const uint64_t *d_sizes, const void *d_hashes /* n_files x 20 B: 4-B aligned */,
+                                uint64_t n_files, int end_files, sf_wire_run **run, uint64_t *bad_file,
+                                void *stream);
+
+/* The sink's FilesList state for one received buffer in one call.  The
+ * longest prefix of whole FILE_ENTRY messages of d_wire[0, n_bytes) (any
+ * address) is parsed as the reference parser reads them (proto.rs:337-364): a
+ * name of 0 to 100 bytes with its newline among the first 101, a size field
+ * that usize::from_str takes in at most 15 bytes with its newline among the
+ * first 16, 20 raw bytes, "\n"; 35 to 149 bytes.  Per entry i, cap rows each:
+ * d_name_at[i] = the name's offset in d_wire, d_name_len[i], d_sizes[i],
+ * d_hashes + 20 i.  *n_out = the entries, *consumed = their bytes, *stop =
+ * SF_WIRE_* for what stands behind them; SF_WIRE_END_FILES: "END_FILES\n"
+ * stood there and is counted in *consumed.  100 name bytes with no newline
+ * among 101, 15 size bytes with none among 16 and another byte than "\n"
+ * behind the hash are SF_WIRE_MALFORMED, not a prefix.  *bad_name = the first
+ * entry whose name is not what Rust's String::from_utf8 takes ("Bad filename
+ * encoding", fs.rs:381-383), UINT64_MAX if none; the entries behind it are
+ * parsed and written all the same, the caller stops there.
+ * With a set, three more outputs: d_rows[i] = sf_name_set_lookup of the name;
+ * d_need[i] = 1 when that is -1, when the row has no recorded hash
+ * (d_have_hash_ok[row] == 0; NULL: every row has one) or when the 20 bytes at
+ * d_have_hashes + 20 row differ from the announced hash in any byte, else 0;
+ * d_need_list[0, *n_need) = the entries with need 1, ascending: the d_pick
+ * sf_wire_get_files_device takes.  With set == NULL the three must be NULL
+ * and the call is a parse only (*n_need = 0).
+ * SF_ENOSPC with *n_out = the need when cap is smaller or an output is NULL:
+ * the first cap rows of the four parsed lists are written (none when an
+ * output is NULL), no row, need or list entry.  Nothing past cap rows is ever
+ * written.  A list that arrives in pieces is continued with the unconsumed
+ * tail plus the new bytes: there is no state to carry.
+ * Every byte position is tested for a whole entry in parallel and the
+ * positions that chain from byte 0 are the entries; a blocks_hash that forges
+ * an entry's start inside the last chained entry is noticed, and the buffer is
+ * then copied back and parsed on the host, serially: the result is the
+ * reference parser's for any input.  Blocking: one read-back for the parse, a
+ * second for *n_need.  n_bytes == 0 launches nothing and needs no device;
+ * n_bytes <= 2^35.  SF_EINVAL, before any device call, for a NULL result
+ * pointer, a NULL d_wire with n_bytes > 0, a lookup output without a set, a
+ * set without d_have_hashes, a d_name_at, d_sizes or d_rows that is not 8-B
+ * aligned, a d_name_len, d_hashes, d_need_list or d_have_hashes that is not
+ * 4-B aligned. */
+int sf_receive_file_entries_device(const sf_name_set *set /* NULL: no lookup */, const void *d_wire,
+                                   uint64_t n_bytes, const void *d_have_hashes /* rows x 20 B: 4-B aligned */,
+                                   const uint8_t *d_have_hash_ok /* may be NULL */, uint64_t *d_name_at,
+                                   uint32_t *d_name_len, uint64_t *d_sizes, void *d_hashes, int64_t *d_rows,
+                                   uint8_t *d_need, uint32_t *d_need_list, uint64_t cap, uint64_t *n_out,
+                                   uint64_t *n_need, uint64_t *bad_name, uint64_t *consumed, int *stop,
+                                   void *stream);
+
+/* The destination's request run: message k is "GET_FILE\n" + name + "\n" of
+ * the name d_bytes[d_name_at[i], + d_name_len[i]) with i = d_pick[k] -- the
+ * spans sf_receive_file_entries_device wrote, read in place from the received
+ * list d_bytes[0, n_bytes) -- for k in [0, n_pick); d_pick == NULL: all n
+ * spans in order (n_pick is not read).  Byte for byte write_message.  *run is
+ * the handle above.  SF_EINVAL with *bad = the first pick whose index is not
+ * below n, whose span leaves the buffer or whose name is over 100 bytes or
+ * holds '\n', and *run = NULL; *bad = UINT64_MAX in every other case.  Lengths,
+ * scan, one read-back, byte stores, as for sf_wire_file_entries_device.  No
+ * message gives an empty run, launches nothing and needs no device.
+ * SF_EINVAL, before any device call, for a NULL run or bad, n or n_pick >
+ * 2^31, a NULL span array with n > 0, a NULL d_bytes with n_bytes > 0, a
+ * d_name_at that is not 8-B aligned, a d_name_len or d_pick that is not 4-B
+ * aligned. */
+int sf_wire_get_files_device(const void *d_bytes, uint64_t n_bytes, const uint64_t *d_name_at,
+                             const uint32_t *d_name_len, uint64_t n, const uint32_t *d_pick /* may be NULL */,
+                             uint64_t n_pick, sf_wire_run **run, uint64_t *bad, void *stream);
 
 /* ----------------------- the destination's missing blocks, on the device ---- */
 

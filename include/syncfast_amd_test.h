@@ -96,6 +96,15 @@ int sf_test_wire_parse_stats(uint64_t out[4]);
  * with calls in flight. */
 int sf_test_recv_files_stats(uint64_t out[4]);
 
+/* What the last sf_receive_file_entries_device of this process did: out[0] the
+ * route (0 the chain on the device, 1 forced to the host by
+ * SF_TEST_WIRE_PARSE_HOST, 2 the host fallback after an entry's start inside
+ * the last chained entry), out[1] the candidate positions the device found (0
+ * when forced to the host), out[2] the chained entries, out[3] the read-backs
+ * (synchronisations of the call: 1 for a parse on the device, 2 with a set).
+ * Host only; not synchronised with calls in flight. */
+int sf_test_file_entries_stats(uint64_t out[4]);
+
 /* What the last BLOCK_DATA parse of this process did (sf_receive_block_data_device
  * / _buffer): out[0] the candidate positions the device found, out[1] the
  * messages, out[2] 1 if the host walked the candidate list (a candidate inside

@@ -28,6 +28,8 @@ SF_ETIMEDOUT = -110
 SF_WIRE_END, SF_WIRE_INCOMPLETE, SF_WIRE_OTHER, SF_WIRE_MALFORMED = 0, 1, 2, 3
 # sf_receive_files_device only: a whole message the sink's state does not take
 SF_WIRE_UNEXPECTED = 4
+# sf_receive_file_entries_device only: END_FILES stood after the last entry
+SF_WIRE_END_FILES = 5
 
 HASH_DIGEST_LEN = 20
 MAX_BLOCK_SIZE = 32 << 20
@@ -130,6 +132,13 @@ def _table():
         "sf_wire_run_to_fd": (i32, [vp, i32, pu64]),
         "sf_wire_run_free": (i32, [vp, vp]),
         "sf_wire_files_device": (i32, [vp, vp, u64, vp, vp, vp, u64, P(vp), pu64, vp]),
+        "sf_name_set_build": (i32, [vp, vp, vp, u64, P(vp), pu64, vp]),
+        "sf_name_set_lookup": (i32, [vp, vp, u64, vp, vp, u64, vp, vp]),
+        "sf_name_set_free": (i32, [vp, vp]),
+        "sf_wire_file_entries_device": (i32, [vp, vp, vp, vp, u64, i32, P(vp), pu64, vp]),
+        "sf_receive_file_entries_device": (i32, [vp, vp, u64, vp, vp, vp, vp, vp, vp, vp, vp, vp, u64, pu64, pu64, pu64,
+                                                 pu64, pint, vp]),
+        "sf_wire_get_files_device": (i32, [vp, u64, vp, vp, u64, vp, u64, P(vp), pu64, vp]),
         "sf_wire_get_blocks_device": (i32, [vp, vp, vp, u64, i32, P(vp), pu64, vp]),
         "sf_place_block_data_device": (i32, [vp, vp, vp, vp, u64, vp, vp, vp, vp, u64, vp, vp, vp, vp, vp, u64, vp,
                                             pu64, pu64, pu64, vp]),
@@ -178,6 +187,7 @@ def _table():
         "sf_test_zpaq_device_stats": (i32, [vp]),
         "sf_test_wire_parse_stats": (i32, [vp]),
         "sf_test_recv_files_stats": (i32, [vp]),
+        "sf_test_file_entries_stats": (i32, [vp]),
         "sf_test_block_data_stats": (i32, [vp]),
         "sf_test_copy_stats": (i32, [vp]),
     }

@@ -53,6 +53,14 @@
 //                 and a parsed BLOCK_DATA run joined against them into a copy
 //                 list (its own kernels; the rules are sf_want_plan.hpp; the
 //                 lookups are sf_match.hip's).
+//   sf_names.hip  the destination's lookup of files by name: the name set
+//                 (its own kernels; the name hash is sf_wire_entries.hpp's).
+//   sf_send_entries.hip  the files list (FILE_ENTRY, END_FILES) and the
+//                 GET_FILE requests built in one call each (its own kernels;
+//                 the rules are sf_wire_entries.hpp).
+//   sf_recv_entries.hip  a received files list parsed, looked up in a name
+//                 set and compared in one call (its own kernels; the rules are
+//                 sf_wire_entries.hpp; the scan is sf_recv_scan.hpp's).
 // Every .hip file launches its kernels and runs its rocprim scans through
 // sf_device.hpp (launch, grid256, scan_inclusive, scan_exclusive), and divides
 // its scratch with sf_layout.hpp (ScratchLayout, for_pieces: host arithmetic,
@@ -113,7 +121,7 @@ enum Knob {
   K_BATCH_FUSED,
   K_TEST_INPLACE_FAIL_AT, K_TEST_WIRE_CHUNK, K_TEST_STREAM_STAGE_MIB, K_TEST_LAUNCH_MAX_BLOCKS, K_TEST_TABLE_SORT,
   K_TEST_MULTI_SELF_GATHER, K_TEST_CUT_WINDOW_MIB, K_TEST_STREAM_POOL, K_TEST_ZPAQ_WINDOW, K_TEST_WIRE_PARSE_HOST,
-  K_TEST_BLOCK_DATA_WALK,
+  K_TEST_BLOCK_DATA_WALK, K_TEST_NAME_HASH_MASK,
   K_COUNT
 };
 struct KnobDef {

@@ -37,6 +37,7 @@ const KnobDef kKnobDefs[K_COUNT] = {
     {"SF_TEST_ZPAQ_WINDOW", 0},         // K_TEST_ZPAQ_WINDOW: sf_index_fd_zpaq's window in bytes (0 = 512 MiB)
     {"SF_TEST_WIRE_PARSE_HOST", 0},     // K_TEST_WIRE_PARSE_HOST: 1 = FILE_BLOCK runs are parsed by the host fallback
     {"SF_TEST_BLOCK_DATA_WALK", 0},     // K_TEST_BLOCK_DATA_WALK: 1 = every BLOCK_DATA run takes the host walk; 2 = and the buffer route parses on the host
+    {"SF_TEST_NAME_HASH_MASK", 0},      // K_TEST_NAME_HASH_MASK: a name set built now ANDs its name hash with this (0 = off)
 };
 
 std::atomic<int64_t> g_knob[K_COUNT];

@@ -33,7 +33,7 @@ __all__ = [
     "fill_splitmix", "splitmix_tensor", "BlockSet", "index_device_multi",
     "cut_device_zpaq", "index_device_zpaq", "zpaq_segment_len", "zpaq_device_stats",
     "copy_blocks", "copy_stats", "write_to_fd", "get_block_requests", "place_block_data",
-    "device_of", "upload",
+    "device_of", "upload", "NameSet", "EntriesReceived", "receive_file_entries", "pack_names", "file_entries_stats",
 ]
 
 
@@ -618,6 +618,194 @@ class BlockSet:
         if self._h:
             with _on(self.table.device, self.stream):
                 check(lib().sf_block_set_free(self._h, _stream_ptr(self.table, self.stream)), "sf_block_set_free")
+            self._h = ctypes.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class EntriesReceived(NamedTuple):
+    """What ``receive_file_entries`` / ``NameSet.receive_entries`` return
+    (sf_receive_file_entries_device), one row per FILE_ENTRY in list order:
+    ``name_at`` int64[n] / ``name_len`` int32[n] the name's bytes in the run,
+    ``sizes`` int64[n] (bit pattern of a uint64), ``hashes`` uint8[n, 20] as
+    announced; with a set ``rows`` int64[n] as ``NameSet.lookup`` gives them,
+    ``need`` uint8[n] and ``need_list`` int32[m] the entries with need 1,
+    ascending (None without a set).  ``consumed`` / ``stop`` as
+    wire.parse_blocks_device (``stop`` may be SF_WIRE_END_FILES: END_FILES was
+    read and is among ``consumed``); ``bad_name`` the first entry whose name
+    is not UTF-8, or None."""
+    name_at: torch.Tensor
+    name_len: torch.Tensor
+    sizes: torch.Tensor
+    hashes: torch.Tensor
+    rows: Optional[torch.Tensor]
+    need: Optional[torch.Tensor]
+    need_list: Optional[torch.Tensor]
+    consumed: int
+    stop: int
+    bad_name: Optional[int]
+
+
+def pack_names(names: Sequence[bytes], device=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """A list of names as the library takes it: (packed bytes uint8, CSR
+    int64[n + 1]) on ``device`` (``device_of``)."""
+    dev = device_of(device)
+    at = np.zeros(len(names) + 1, np.int64)
+    np.cumsum(np.fromiter((len(n) for n in names), np.int64, len(names)), out=at[1:])
+    return upload(b"".join(bytes(n) for n in names), dev), torch.from_numpy(at).to(dev)
+
+
+def file_entries_stats() -> Tuple[int, int, int, int]:
+    """Test hook (sf_test_file_entries_stats): (route: 0 the device chain, 1
+    forced to the host, 2 the host fallback; candidates; chained entries;
+    read-backs) of this process's last sf_receive_file_entries_device."""
+    out = (ctypes.c_uint64 * 4)()
+    check(lib().sf_test_file_entries_stats(out), "sf_test_file_entries_stats")
+    return tuple(int(v) for v in out)
+
+
+def receive_file_entries(run: torch.Tensor, name_set: Optional["NameSet"] = None,
+                         have_hashes: Optional[torch.Tensor] = None, have_hash_ok: Optional[torch.Tensor] = None,
+                         stream: Optional[torch.cuda.Stream] = None) -> EntriesReceived:
+    """The sink's FilesList state for one received buffer, in one call
+    (sf_receive_file_entries_device): the FILE_ENTRY messages at the start of
+    ``run`` (a flat uint8 HBM tensor) parsed on the device as ``wire.Parser``
+    reads them.  With ``name_set`` every name is looked up in it and every
+    announced hash compared with ``have_hashes`` uint8[rows, 20] (the recorded
+    blocks_hash of the set's rows; ``have_hash_ok`` uint8/bool[rows], None =
+    every row has one): see ``EntriesReceived``.  A list that arrives in pieces
+    is continued with ``run[consumed:]`` + the new bytes.  Blocking."""
+    _require_device(run, "run", torch.uint8)
+    if run.dim() != 1:
+        raise ValueError("run must be a flat uint8 tensor")
+    dev = run.device
+    h = None
+    if name_set is not None:
+        if not name_set._h:
+            raise ValueError("NameSet is closed")
+        rows_n = name_set.n_rows
+        if have_hashes is None:
+            raise ValueError("a name set needs have_hashes")
+        _require_device(have_hashes, "have_hashes", torch.uint8, dev)
+        if have_hashes.numel() != 20 * rows_n:
+            raise ValueError("have_hashes must be uint8[rows, 20]")
+        have_hash_ok = _flags(have_hash_ok, "have_hash_ok", rows_n, dev)
+        h, stream = name_set._h, stream if stream is not None else name_set.stream
+    elif have_hashes is not None or have_hash_ok is not None:
+        raise ValueError("have_hashes and have_hash_ok go with a name set")
+    n, n_need, bad, consumed = (ctypes.c_uint64(0) for _ in range(4))
+    stop = ctypes.c_int(0)
+    cap = run.numel() // 35 + 1  # an entry is at least 35 bytes
+    with _on(dev, stream):
+        e = lambda k, t: torch.empty(k, dtype=t, device=dev)  # noqa: E731
+        name_at, name_len, sizes, hashes = e(cap, torch.int64), e(cap, torch.int32), e(cap, torch.int64), e(
+            (cap, 20), torch.uint8)
+        rows, need, need_list = (e(cap, torch.int64), e(cap, torch.uint8), e(cap, torch.int32)) if h else (None,) * 3
+        # the library wants a table even when the set has no row
+        have = have_hashes if h is None or have_hashes.numel() else e(20, torch.uint8)
+        check(lib().sf_receive_file_entries_device(
+            h, _ptr(run), run.numel(), have.data_ptr() if h else None, _ptr(have_hash_ok), name_at.data_ptr(),
+            name_len.data_ptr(), sizes.data_ptr(), hashes.data_ptr(), _ptr(rows), _ptr(need), _ptr(need_list), cap,
+            ctypes.byref(n), ctypes.byref(n_need), ctypes.byref(bad), ctypes.byref(consumed), ctypes.byref(stop),
+            _stream_ptr(run, stream)), "sf_receive_file_entries_device")
+    k, m = n.value, n_need.value
+    return EntriesReceived(name_at[:k], name_len[:k], sizes[:k], hashes[:k], rows[:k] if h else None,
+                           need[:k] if h else None, need_list[:m] if h else None, consumed.value, stop.value,
+                           None if bad.value == (1 << 64) - 1 else bad.value)
+
+
+class NameSet:
+    """The receiving side's lookup of files by name, on the device
+    (sf_name_set_*): Index::get_file for a whole files list at once, the
+    sibling of ``BlockSet``.
+
+    Built from a destination index's file rows in file_id order -- ``names``
+    uint8 the packed name bytes, ``name_at`` int64[n + 1] the CSR into them
+    (``pack_names`` makes both from a list; ``NameSet.build`` does it all),
+    ``present`` bool/uint8[n] (None = all; the mirror of temporary = 0).
+    ``lookup`` gives for each query the lowest present row of that name, or
+    -1 (SQLite's idx_files_name order: the schema has no UNIQUE on name).  A
+    CSR that does not hold raises ValueError naming the first bad row.  The
+    set reads ``names`` and ``name_at`` at lookup time: keep them unchanged
+    while in use."""
+
+    def __init__(self, names: torch.Tensor, name_at: torch.Tensor, present: Optional[torch.Tensor] = None,
+                 stream: Optional[torch.cuda.Stream] = None):
+        _require_device(names, "names", torch.uint8)
+        dev = names.device
+        _require_device(name_at, "name_at", torch.int64, dev)
+        if names.dim() != 1 or name_at.dim() != 1 or name_at.numel() < 1:
+            raise ValueError("names must be flat and name_at hold one entry per row and one more")
+        n = name_at.numel() - 1
+        present = _flags(present, "present", n, dev)
+        self.names, self.name_at, self.present, self.stream, self.n_rows = names, name_at, present, stream, n
+        self._h = ctypes.c_void_p()
+        bad = ctypes.c_uint64(0)
+        with _on(dev, stream):
+            rc = lib().sf_name_set_build(_ptr(names), name_at.data_ptr(), _ptr(present), n, ctypes.byref(self._h),
+                                         ctypes.byref(bad), _stream_ptr(names, stream))
+        if rc != 0 and bad.value != (1 << 64) - 1:
+            raise ValueError(f"row {bad.value}: its name_at entries do not hold")
+        check(rc, "sf_name_set_build")
+
+    @classmethod
+    def build(cls, names: Sequence[bytes], present=None, device=None,
+              stream: Optional[torch.cuda.Stream] = None) -> "NameSet":
+        """The set of a list of names (bytes), row i = ``names[i]``;
+        ``present`` a sequence of flags or None."""
+        dev = device_of(device)
+        packed, at = pack_names(names, dev)
+        if present is not None and not isinstance(present, torch.Tensor):
+            present = torch.from_numpy(np.asarray(present, dtype=np.uint8)).to(dev)
+        return cls(packed, at, present, stream)
+
+    def lookup(self, data: torch.Tensor, at: torch.Tensor, lens: torch.Tensor) -> torch.Tensor:
+        """int64[m]: for query i, the ``lens[i]`` bytes of ``data`` (flat uint8)
+        from ``at[i]`` -- ``at`` int64[m], ``lens`` int32/uint32[m], spans
+        anywhere in ``data`` -- the lowest present row of that name, or -1.  A
+        span that leaves ``data`` gives -1."""
+        dev = self.names.device
+        _require_device(data, "data", torch.uint8, dev)
+        m = at.numel()
+        _list64(at, "at", m, dev)
+        _list32(lens, "lens", m, dev)
+        if not self._h:
+            raise ValueError("NameSet is closed")
+        with _on(dev, self.stream):
+            rows = torch.empty(m, dtype=torch.int64, device=dev)
+            if m:
+                check(lib().sf_name_set_lookup(self._h, _ptr(data), data.numel(), at.data_ptr(), lens.data_ptr(), m,
+                                               rows.data_ptr(), _stream_ptr(self.names, self.stream)),
+                      "sf_name_set_lookup")
+        return rows
+
+    def lookup_names(self, names: Sequence[bytes]) -> torch.Tensor:
+        """``lookup`` of a list of names (bytes)."""
+        dev = self.names.device
+        with _on(dev, self.stream):
+            packed, at = pack_names(names, dev)
+            lens = (at[1:] - at[:-1]).to(torch.int32)
+            return self.lookup(packed, at[:-1].contiguous(), lens)
+
+    def receive_entries(self, run: torch.Tensor, have_hashes: torch.Tensor,
+                        have_hash_ok: Optional[torch.Tensor] = None) -> EntriesReceived:
+        """``receive_file_entries`` of ``run`` against this set."""
+        return receive_file_entries(run, self, have_hashes, have_hash_ok)
+
+    def close(self) -> None:
+        if self._h:
+            with _on(self.names.device, self.stream):
+                check(lib().sf_name_set_free(self._h, _stream_ptr(self.names, self.stream)), "sf_name_set_free")
             self._h = ctypes.c_void_p()
 
     def __enter__(self):

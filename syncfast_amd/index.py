@@ -760,6 +760,180 @@ class Index:
                                 packed, name_at.view(torch.int64))
         return run, len(files)
 
+    def file_entries(self, device=None):
+        """The source's ``ListFiles`` state over ``list_files()``
+        (src/sync/fs.rs:133-164): one FILE_ENTRY per file -- name, size,
+        blocks_hash -- in that order, then END_FILES.  ``device=None`` is the
+        definition, the ``write_message`` loop, and returns bytes.  With a
+        device the names, sizes and hashes go up in one upload and ONE
+        ``wire.file_entries_device`` call (sf_wire_file_entries_device) builds
+        the list in HBM: a ``wire.EntriesRun`` (``bytes()``, ``to_fd(fd)``,
+        ``receive``, ``close()``).  Both routes raise SyncfastError for the
+        first file the protocol cannot carry -- a name over 100 bytes or with
+        a newline, a size of 10^15 or more, no blocks_hash -- where the
+        reference would send the entry and its peer would raise mid-list."""
+        from . import wire
+        files = []
+        for _file_id, path, _modified, size, blocks_hash in self.list_files():
+            raw = str(path).encode("utf-8")
+            if len(raw) > wire.FILENAME_MAX or b"\n" in raw or size >= 10 ** wire.SIZE_MAX or blocks_hash is None:
+                raise SyncfastError("The protocol cannot carry file %r (name, size or no blocks_hash)" % str(path))
+            files.append((raw, size, blocks_hash))
+        if device is None:
+            return b"".join(wire.write_message("FileEntry", *f) for f in files) + wire.write_message("EndFiles")
+        import torch
+
+        from .device import device_of, upload
+        dev = device_of(device)
+        # one buffer, widest elements first so that every part starts on its own grid
+        parts = [np.cumsum([0] + [len(raw) for raw, _s, _h in files], dtype=np.int64).tobytes(),
+                 np.fromiter((s for _raw, s, _h in files), np.int64, len(files)).tobytes(),
+                 b"".join(h.bytes for _raw, _s, h in files), b"".join(raw for raw, _s, _h in files)]
+        buf = upload(b"".join(parts), dev)
+        at = np.cumsum([0] + [len(p) for p in parts]).tolist()
+        name_at, sizes, hashes, packed = (buf[a:b] for a, b in zip(at, at[1:]))
+        return wire.file_entries_device(packed, name_at.view(torch.int64), sizes.view(torch.int64),
+                                        hashes.reshape(len(files), 20))
+
+    @staticmethod
+    def _entries_on_host(data: bytes):
+        """The FILE_ENTRY messages ``wire.Parser`` reads from byte 0 of
+        ``data`` -> ([(name, size, hash)], consumed, stop): ``stop`` the
+        SF_WIRE_* class of what stands behind them, SF_WIRE_END_FILES with
+        END_FILES read and counted."""
+        from . import wire
+        p = wire.Parser()
+        p._buf = bytearray(data)
+        entries, pos = [], 0
+        while True:
+            if pos == len(data):
+                return entries, pos, wire.SF_WIRE_END
+            try:
+                line = p._line(pos, wire.COMMAND_MAX, "Unterminated command")
+                if line is None:
+                    return entries, pos, wire.SF_WIRE_INCOMPLETE
+                if line[0] in (b"GET_FILE", b"FILE_START", b"FILE_END", b"GET_BLOCK", b"FILE_BLOCK", b"BLOCK_DATA",
+                               b"COMPLETE"):  # another command's complete line, whatever follows it
+                    return entries, pos, wire.SF_WIRE_OTHER
+                r = p._one(pos)  # an unknown command raises
+            except wire.ProtocolError:
+                return entries, pos, wire.SF_WIRE_MALFORMED
+            if r is None:
+                return entries, pos, wire.SF_WIRE_INCOMPLETE
+            msg, pos = r
+            if msg[0] == "EndFiles":
+                return entries, pos, wire.SF_WIRE_END_FILES
+            entries.append(msg[1:])
+
+    def _requests_on_host(self) -> bytes:
+        """The GET_FILE messages of fs.rs:415-443: one per ``list_temp_files()``
+        row, in that order."""
+        from . import wire
+        return b"".join(wire.write_message("GetFile", str(untemp_name(t)).encode("utf-8")) for t in self.list_temp_files())
+
+    def receive_file_entries(self, data, device=None):
+        """The sink's ``FilesList`` state for one received buffer
+        (src/sync/fs.rs:378-446): every FILE_ENTRY at the start of ``data`` is
+        looked up by name (``get_file``), its announced blocks_hash compared
+        with the recorded one, and ``add_temp_file`` run for it when they
+        differ, when none is recorded or when the file is unknown; END_FILES
+        ends the list.  Returns (n_entries, consumed, stop, needed_names,
+        requests): ``consumed`` / ``stop`` as ``wire.parse_blocks_device``
+        (``stop`` is SF_WIRE_END_FILES once END_FILES was read; a list that
+        arrives in pieces is continued with ``data[consumed:]`` + the new
+        bytes), ``needed_names`` the names (bytes) of the entries that got a
+        temp row, in entry order -- creating those files on disk stays with
+        the caller -- and ``requests`` the GET_FILE run for
+        ``list_temp_files()`` in that order once END_FILES was read, else None.
+        A name that is not UTF-8 raises SyncfastError("Bad filename
+        encoding") after the entries before it have been applied, as the
+        reference does.
+
+        ``device=None`` is the reference's loop message by message and the
+        definition; ``requests`` is bytes.  With a device the destination's
+        non-temporary rows go up once, one ``device.NameSet`` is built, ONE
+        sf_receive_file_entries_device call parses, looks up and compares the
+        whole buffer, ``add_temp_file`` runs per needed entry in entry order
+        (the database stays SQLite's), and ``requests`` is a
+        ``wire.GetFilesRun`` built from the received names in place
+        (sf_wire_get_files_device): from the call's need list when
+        ``list_temp_files()`` is exactly the needed entries in order, else
+        from an explicit pick, with the names of leftover temp rows of an
+        earlier sync uploaded behind the list.  One lookup for the whole list
+        equals the loop unless the index holds a non-temporary file whose last
+        component starts with ``.syncfast_tmp_``: ``add_temp_file`` resets such
+        a row to temporary (src/index.rs:262-300), and a later entry's
+        ``get_file`` would see that.  Such an index takes the loop."""
+        from . import wire
+        data = bytes(data)
+        if device is not None and not any(PurePath(r[0]).name.startswith(TEMP_PREFIX) for r in self.db.execute(
+                "SELECT name FROM files WHERE temporary = 0 AND name LIKE ?;", ("%" + TEMP_PREFIX + "%",))):
+            return self._receive_file_entries_device(data, device)
+        entries, consumed, stop = self._entries_on_host(data)
+        needed = []
+        for name, _size, blocks_hash in entries:
+            try:
+                path = PurePath(name.decode("utf-8"))
+            except UnicodeDecodeError:
+                raise SyncfastError("Bad filename encoding") from None
+            found = self.get_file(path)
+            if found is None or found[2] != blocks_hash:
+                self.add_temp_file(path)
+                needed.append(name)
+        requests = self._requests_on_host() if stop == wire.SF_WIRE_END_FILES else None
+        return len(entries), consumed, stop, needed, requests
+
+    def _receive_file_entries_device(self, data: bytes, device):
+        import torch
+
+        from . import wire
+        from .device import NameSet, device_of, upload
+        dev = device_of(device)
+        rows = self.db.execute("SELECT name, blocks_hash FROM files WHERE temporary = 0 ORDER BY file_id;").fetchall()
+        names = [str(PurePath(r[0])).encode("utf-8") for r in rows]
+        hashes = [HashDigest.from_sql(r[1]).bytes if r[1] is not None else bytes(20) for r in rows]
+        # one upload: the CSR first (8-B entries), then hashes, flags and names
+        parts = [np.cumsum([0] + [len(n) for n in names], dtype=np.int64).tobytes(), b"".join(hashes),
+                 bytes(r[1] is not None for r in rows), b"".join(names)]
+        buf = upload(b"".join(parts), dev)
+        at = np.cumsum([0] + [len(p) for p in parts]).tolist()
+        name_at, have, have_ok, packed = (buf[a:b] for a, b in zip(at, at[1:]))
+        run = upload(data, dev)
+        with NameSet(packed, name_at.view(torch.int64)) as ns:
+            got = ns.receive_entries(run, have.reshape(len(rows), 20), have_ok)
+        n = int(got.name_at.numel())
+        starts, lens = got.name_at.cpu().tolist(), got.name_len.cpu().tolist()
+        need = got.need_list.cpu().tolist()
+        if got.bad_name is not None:
+            need = [i for i in need if i < got.bad_name]
+        needed = [data[starts[i]:starts[i] + lens[i]] for i in need]
+        for name in needed:
+            self.add_temp_file(PurePath(name.decode("utf-8")))
+        if got.bad_name is not None:
+            raise SyncfastError("Bad filename encoding")
+        if got.stop != wire.SF_WIRE_END_FILES:
+            return n, got.consumed, got.stop, needed, None
+        want = [str(untemp_name(t)).encode("utf-8") for t in self.list_temp_files()]
+        if want == needed:  # the temp rows are exactly the needed entries, in order: the call's own list picks them
+            requests = wire.get_files_device(run, got.name_at, got.name_len, got.need_list)
+            return n, got.consumed, got.stop, needed, requests
+        # leftover temp rows, or names the index spells otherwise: their bytes go behind the list
+        where = {}
+        for i, name in zip(need, needed):
+            where.setdefault(name, i)
+        extra, spans, pick = b"", [], []
+        for name in want:
+            if name not in where:
+                where[name] = n + len(spans)
+                spans.append((len(data) + len(extra), len(name)))
+                extra += name
+            pick.append(where[name])
+        both = torch.cat([run, upload(extra, dev)])
+        at2 = torch.cat([got.name_at, torch.tensor([a for a, _l in spans], dtype=torch.int64, device=dev)])
+        len2 = torch.cat([got.name_len, torch.tensor([ln for _a, ln in spans], dtype=torch.int32, device=dev)])
+        requests = wire.get_files_device(both, at2, len2, torch.tensor(pick, dtype=torch.int32, device=dev))
+        return n, got.consumed, got.stop, needed, requests
+
     def get_file(self, name) -> Optional[Tuple[int, DateTimeUtc, Optional[HashDigest]]]:
         row = self.db.execute(
             "SELECT file_id, modified, blocks_hash FROM files WHERE name = ? AND temporary = 0;",

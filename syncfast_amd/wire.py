@@ -20,7 +20,7 @@ import re
 from typing import List, Tuple
 
 from ._lib import (SF_ENOSPC, SF_OK, SF_WIRE_END, SF_WIRE_INCOMPLETE, SF_WIRE_MALFORMED,  # noqa: F401
-                   SF_WIRE_OTHER, SF_WIRE_UNEXPECTED, check, lib)
+                   SF_WIRE_END_FILES, SF_WIRE_OTHER, SF_WIRE_UNEXPECTED, check, lib)
 from .digest import HashDigest
 
 
@@ -466,6 +466,98 @@ def files_device(digests, sizes, file_first, names, name_at, stream=None) -> Fil
                          f"{FILENAME_MAX} bytes or holds a newline")
     check(rc, "sf_wire_files_device")
     return FilesRun(h, d, stream)
+
+
+class EntriesRun(BlockDataRun):
+    """A files list built in HBM (``file_entries_device``,
+    ``Index.file_entries``): FILE_ENTRY after FILE_ENTRY and END_FILES in one
+    library-owned run.  ``BlockDataRun`` in everything but what ``receive``
+    does with it."""
+
+    def receive(self, name_set=None, have_hashes=None, have_hash_ok=None):
+        """The run handed straight to ``device.receive_file_entries``
+        (sf_receive_file_entries_device) -- the destination's half of the
+        exchange -- and its ``EntriesReceived``."""
+        from . import device
+        return device.receive_file_entries(self.tensor(), name_set, have_hashes, have_hash_ok,
+                                           stream=None if name_set is not None else self.stream)
+
+
+class GetFilesRun(BlockDataRun):
+    """The destination's GET_FILE requests built in HBM (``get_files_device``,
+    ``Index.receive_file_entries``).  ``BlockDataRun``, but ``receive`` has no
+    device route yet: the source parses the requests with ``Parser``."""
+
+    def receive(self, *args, **kwargs):
+        return Parser().receive(self.bytes())
+
+
+def file_entries_device(names, name_at, sizes, hashes, end_files: bool = True, stream=None) -> EntriesRun:
+    """The source's files list, built on the device in one call
+    (sf_wire_file_entries_device): for file f ``write_message("FileEntry",
+    name, size, hash)``, file after file, and ``write_message("EndFiles")``
+    behind them with ``end_files``, byte for byte.  ``names`` uint8 the packed
+    name bytes, ``name_at`` int64[n + 1] the CSR into them
+    (``device.pack_names``), ``sizes`` int64[n], ``hashes`` uint8[n, 20]: HBM
+    tensors on one device.  A broken CSR, a name the protocol cannot carry (over
+    100 bytes, or holding a newline) or a size of 10^15 or more raises
+    ValueError naming the first such file, and nothing is built.  Blocking, for
+    one read-back."""
+    torch, dev = _device(names, "names")
+    d = names.device
+    dev._require_device(name_at, "name_at", torch.int64, d)
+    dev._require_device(sizes, "sizes", torch.int64, d)
+    dev._require_device(hashes, "hashes", torch.uint8, d)
+    n = name_at.numel() - 1
+    if n < 0 or names.dim() != 1 or name_at.dim() != 1 or sizes.numel() != n or hashes.numel() != 20 * n:
+        raise ValueError("name_at holds one entry per file and one more, sizes one and hashes 20 bytes per file")
+    h, bad = ctypes.c_void_p(), ctypes.c_uint64(0)
+    with dev._on(d, stream):
+        rc = lib().sf_wire_file_entries_device(dev._ptr(names), name_at.data_ptr(), dev._ptr(sizes, n),
+                                               dev._ptr(hashes, n), n, int(bool(end_files)), ctypes.byref(h),
+                                               ctypes.byref(bad), _stream(torch, names))
+    if rc != SF_OK and bad.value != (1 << 64) - 1:
+        raise ValueError(f"file {bad.value}: its name entries do not hold, its name is over {FILENAME_MAX} bytes or "
+                         f"holds a newline, or its size has more than {SIZE_MAX} digits")
+    check(rc, "sf_wire_file_entries_device")
+    return EntriesRun(h, d, stream)
+
+
+def get_files_device(data, name_at, name_len, pick=None, stream=None) -> GetFilesRun:
+    """The destination's request run, built on the device in one call
+    (sf_wire_get_files_device): ``write_message("GetFile", name)`` of the
+    names ``data[name_at[i] : + name_len[i]]`` for i in ``pick`` (int32/uint32,
+    in that order, repeats allowed; None: every span in order) -- ``data`` the
+    received list as a flat uint8 HBM tensor, the spans as
+    ``device.receive_file_entries`` returns them, ``pick`` its ``need_list``.
+    An index outside the spans, a span that leaves ``data`` or a name the
+    protocol cannot carry raises ValueError naming the first such pick.
+    Blocking, for one read-back."""
+    torch, dev = _device(data, "data")
+    d = data.device
+    n = name_at.numel()
+    dev._list64(name_at, "name_at", n, d)
+    dev._list32(name_len, "name_len", n, d)
+    if pick is not None:
+        dev._list32(pick, "pick", pick.numel(), d)
+    h, bad = ctypes.c_void_p(), ctypes.c_uint64(0)
+    with dev._on(d, stream):
+        # the library wants an array for an explicit pick of nothing
+        p = None if pick is None else (pick if pick.numel() else torch.zeros(1, dtype=torch.int32, device=d))
+        rc = lib().sf_wire_get_files_device(dev._ptr(data), data.numel(), dev._ptr(name_at), dev._ptr(name_len), n,
+                                            None if p is None else p.data_ptr(), 0 if pick is None else pick.numel(),
+                                            ctypes.byref(h), ctypes.byref(bad), _stream(torch, data))
+    if rc != SF_OK and bad.value != (1 << 64) - 1:
+        raise ValueError(f"pick {bad.value}: its index or its span is out of range, or its name is over "
+                         f"{FILENAME_MAX} bytes or holds a newline")
+    check(rc, "sf_wire_get_files_device")
+    return GetFilesRun(h, d, stream)
+
+
+def file_entries_stats():
+    """Test hook (sf_test_file_entries_stats): see ``device.file_entries_stats``."""
+    from . import device
+    return device.file_entries_stats()
 
 
 def blocks_to_fd(digests, sizes, fd: int, stream=None) -> int:
