@@ -737,6 +737,106 @@ int sf_wire_get_files_device(const void *d_bytes, uint64_t n_bytes, const uint64
                              const uint32_t *d_name_len, uint64_t n, const uint32_t *d_pick /* may be NULL */,
                              uint64_t n_pick, sf_wire_run **run, uint64_t *bad, void *stream);
 
+/* ------------------- answering a received GET_FILE run, on the device ---- */
+
+/* The source's side of those requests (src/sync/fs.rs:177-231): a received run
+ * of GET_FILE messages parsed, and answered, in one call each
+ * (sf_serve_files.hip).  With sf_serve_get_blocks_device every
+ * request the source receives is then answered in HBM from the received bytes. */
+
+/* The inverse of sf_wire_get_files_device.  The longest prefix of whole
+ * GET_FILE messages of d_wire[0, n_bytes) (any address) is parsed as the
+ * reference parser reads them (proto.rs:365-376): "GET_FILE\n", a name of 0 to
+ * 100 bytes with its newline among the first 101; 10 to 110 bytes.  Per
+ * request i, cap rows each: d_name_at[i] = the name's offset in d_wire,
+ * d_name_len[i] -- the spans sf_name_set_lookup takes.  *n_out = the requests,
+ * *consumed = their bytes, *stop = SF_WIRE_* for what stands behind them: 100
+ * name bytes with no newline (also when only those 100 are there yet), 20
+ * command bytes with none and an unknown command are SF_WIRE_MALFORMED, the
+ * complete command line of one of the other eight commands SF_WIRE_OTHER.
+ * *bad_name = the first request whose name is not what Rust's String::from_utf8
+ * takes ("Bad filename encoding", fs.rs:181-183), UINT64_MAX if none; the
+ * requests behind it are parsed and written all the same.
+ * SF_ENOSPC with *n_out = the need when cap is smaller or an output is NULL:
+ * the first cap rows are written (none when an output is NULL).  Nothing past
+ * cap rows is ever written.  A run that arrives in pieces is continued with
+ * the unconsumed tail plus the new bytes: there is no state to carry.
+ * A name holds no newline, so request k is lines 2k and 2k + 1 of the buffer:
+ * the newlines are found and counted in parallel, one lane per 64 positions
+ * judges its newlines' lines by the parity of their index, and the first
+ * failing line is an atomic minimum.  No position is guessed, so no input can
+ * forge a request and there is no host fallback: the result is the reference
+ * parser's for any input.  Blocking: one read-back.  n_bytes == 0 launches
+ * nothing and needs no device; n_bytes <= 2^35.  SF_EINVAL, before any device
+ * call, for a NULL result pointer, a NULL d_wire with n_bytes > 0, a d_name_at
+ * that is not 8-B aligned or a d_name_len that is not 4-B aligned. */
+int sf_wire_parse_get_files_device(const void *d_wire, uint64_t n_bytes, uint64_t *d_name_at,
+                                   uint32_t *d_name_len, uint64_t cap, uint64_t *n_out,
+                                   uint64_t *bad_name, uint64_t *consumed, int *stop, void *stream);
+
+/* Why sf_serve_get_files_device stopped answering (*why). */
+enum {
+    SF_SERVE_ALL = 0,      /* every request was answered */
+    SF_SERVE_BAD_NAME = 1, /* the next request's name is not UTF-8 ("Bad filename encoding"; the
+                              reference checks this first, so it wins over SF_SERVE_UNKNOWN) */
+    SF_SERVE_UNKNOWN = 2,  /* the set does not hold the next request's name ("Requested file is
+                              unknown") */
+    SF_SERVE_FULL = 3      /* with the next answer the run would exceed max_run_bytes, or 2^32
+                              messages: send the run and call again from *answered_bytes */
+};
+
+/* A received run of GET_FILE requests answered in one call.  The source's
+ * tables stay in HBM for the whole sync: `set`, the name set over its
+ * non-temporary files in file_id order, and a CSR of those rows into the
+ * index's own block table: row r owns blocks [d_file_first[r], d_file_first[r
+ * + 1]) of d_digests (20 B each) and d_sizes, in list_file_blocks order.
+ * Nothing is gathered on the host and no digest is copied in HBM: the kernels
+ * read the table through request -> row -> block.
+ * d_requests[0, n_bytes) is parsed as by sf_wire_parse_get_files_device:
+ * *n_requests, *consumed and *stop describe the whole parsed prefix.  Every
+ * name is looked up in the set (sf_name_set_lookup: the lowest present row,
+ * Index::get_file) and request k becomes FILE_START with the name's bytes
+ * (read in place from d_requests), one FILE_BLOCK per block of its row and
+ * FILE_END -- the messages of sf_wire_files_device, byte for byte what the
+ * reference writes.  A repeated request is answered each time; an empty file
+ * gives two messages.  Requests [0, *n_answered) are answered, up to the first
+ * that cannot be, and *why (SF_SERVE_*) says what stopped it; *answered_bytes
+ * = the bytes of d_requests those requests occupy.  The caller sends the run
+ * and then raises what *why names, as the reference does, or after
+ * SF_SERVE_FULL calls again with the requests from *answered_bytes on.
+ * max_run_bytes (0: no bound) bounds the run: a peer can repeat one large
+ * file's name, the reference streams its answer, and this call allocates it.
+ * The answered prefix is the longest whose run fits.
+ * The row of the request where answering stops, when its name is UTF-8 and
+ * known, must hold: d_file_first[r] <= d_file_first[r + 1] <= n_blocks.  Else
+ * SF_EINVAL with *bad_row = that row and *run = NULL; nothing is kept allocated
+ * and no byte outside the arrays as described is loaded (such a row's blocks
+ * are never read).  *bad_row = UINT64_MAX in every other case.  Rows no request
+ * names are never read.
+ * Parse, lookup, per-request block counts and their scan, a coarse stop (every
+ * block at its shortest) and the stop before it, the block sizes gathered in
+ * answer order and their lengths' 64-bit scan, the exact stop, allocation,
+ * frames, blocks: every step a kernel, each block finding its request by an
+ * upper-bound binary search of the request CSR, every first-stop an atomic
+ * minimum with one atomic per wave.  Blocking: THREE read-backs, whatever the
+ * number of requests (the parse; the coarse stop and its block count; the
+ * answered requests and the run's length) -- one when no request was parsed,
+ * two or three when none is answered.  Scratch: 20 bytes per 10 request bytes, 32 per
+ * request, 20 per answered block, plus the scans'.  n_bytes == 0 gives an
+ * empty run and SF_WIRE_END, launches nothing and needs no device; no
+ * answered request gives an empty run too.  n_bytes <= 2^35, n_blocks <= 2^32.
+ * SF_EINVAL, before any device call, for a NULL result pointer, a NULL set,
+ * d_requests or d_file_first with n_bytes > 0, a NULL d_digests or d_sizes
+ * with n_bytes > 0 and n_blocks > 0, a d_file_first that is not 8-B aligned, a
+ * d_digests or d_sizes that is not 4-B aligned. */
+int sf_serve_get_files_device(const sf_name_set *set, const uint64_t *d_file_first /* set rows + 1 */,
+                              const void *d_digests /* n_blocks x 20 B: 4-B aligned */,
+                              const uint32_t *d_sizes, uint64_t n_blocks, const void *d_requests,
+                              uint64_t n_bytes, uint64_t max_run_bytes /* 0: no bound */,
+                              sf_wire_run **run, uint64_t *n_requests, uint64_t *n_answered,
+                              uint64_t *answered_bytes, int *why, uint64_t *bad_row,
+                              uint64_t *consumed, int *stop, void *stream);
+
 /* ----------------------- the destination's missing blocks, on the device ---- */
 
 /* The two steps between the runs.  After the FILE_BLOCK runs the sink lists

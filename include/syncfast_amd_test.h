@@ -105,6 +105,15 @@ int sf_test_recv_files_stats(uint64_t out[4]);
  * Host only; not synchronised with calls in flight. */
 int sf_test_file_entries_stats(uint64_t out[4]);
 
+/* What the last sf_serve_get_files_device of this process did: out[0] the route
+ * (0 nothing launched: no bytes or an argument error; 1 parsed, and no request
+ * answered: an empty run; 2 a run built), out[1] the requests parsed, out[2]
+ * the requests answered, out[3] the read-backs (synchronisations of the call:
+ * 3 for a run built, whatever the number of requests; 1 when no request was
+ * parsed, 2 or 3 when none is answered).  Host only; not
+ * synchronised with calls in flight. */
+int sf_test_serve_files_stats(uint64_t out[4]);
+
 /* What the last BLOCK_DATA parse of this process did (sf_receive_block_data_device
  * / _buffer): out[0] the candidate positions the device found, out[1] the
  * messages, out[2] 1 if the host walked the candidate list (a candidate inside

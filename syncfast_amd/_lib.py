@@ -30,6 +30,8 @@ SF_WIRE_END, SF_WIRE_INCOMPLETE, SF_WIRE_OTHER, SF_WIRE_MALFORMED = 0, 1, 2, 3
 SF_WIRE_UNEXPECTED = 4
 # sf_receive_file_entries_device only: END_FILES stood after the last entry
 SF_WIRE_END_FILES = 5
+# Why sf_serve_get_files_device stopped answering
+SF_SERVE_ALL, SF_SERVE_BAD_NAME, SF_SERVE_UNKNOWN, SF_SERVE_FULL = 0, 1, 2, 3
 
 HASH_DIGEST_LEN = 20
 MAX_BLOCK_SIZE = 32 << 20
@@ -139,6 +141,9 @@ def _table():
         "sf_receive_file_entries_device": (i32, [vp, vp, u64, vp, vp, vp, vp, vp, vp, vp, vp, vp, u64, pu64, pu64, pu64,
                                                  pu64, pint, vp]),
         "sf_wire_get_files_device": (i32, [vp, u64, vp, vp, u64, vp, u64, P(vp), pu64, vp]),
+        "sf_wire_parse_get_files_device": (i32, [vp, u64, vp, vp, u64, pu64, pu64, pu64, pint, vp]),
+        "sf_serve_get_files_device": (i32, [vp, vp, vp, vp, u64, vp, u64, u64, P(vp), pu64, pu64, pu64, pint, pu64, pu64,
+                                            pint, vp]),
         "sf_wire_get_blocks_device": (i32, [vp, vp, vp, u64, i32, P(vp), pu64, vp]),
         "sf_place_block_data_device": (i32, [vp, vp, vp, vp, u64, vp, vp, vp, vp, u64, vp, vp, vp, vp, vp, u64, vp,
                                             pu64, pu64, pu64, vp]),
@@ -188,6 +193,7 @@ def _table():
         "sf_test_wire_parse_stats": (i32, [vp]),
         "sf_test_recv_files_stats": (i32, [vp]),
         "sf_test_file_entries_stats": (i32, [vp]),
+        "sf_test_serve_files_stats": (i32, [vp]),
         "sf_test_block_data_stats": (i32, [vp]),
         "sf_test_copy_stats": (i32, [vp]),
     }

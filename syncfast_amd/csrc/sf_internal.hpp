@@ -61,6 +61,11 @@
 //   sf_recv_entries.hip  a received files list parsed, looked up in a name
 //                 set and compared in one call (its own kernels; the rules are
 //                 sf_wire_entries.hpp; the scan is sf_recv_scan.hpp's).
+//   sf_serve_files.hip  a received run of GET_FILE requests parsed, and
+//                 answered from the index's own block table in one call (its
+//                 own kernels; the rules are sf_wire_get_files.hpp; the newline
+//                 bitmap is sf_recv_scan.hpp's, the lookup sf_names.hip's, the
+//                 block scan sf_wire.hip's).
 // Every .hip file launches its kernels and runs its rocprim scans through
 // sf_device.hpp (launch, grid256, scan_inclusive, scan_exclusive), and divides
 // its scratch with sf_layout.hpp (ScratchLayout, for_pieces: host arithmetic,

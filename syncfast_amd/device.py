@@ -34,6 +34,7 @@ __all__ = [
     "cut_device_zpaq", "index_device_zpaq", "zpaq_segment_len", "zpaq_device_stats",
     "copy_blocks", "copy_stats", "write_to_fd", "get_block_requests", "place_block_data",
     "device_of", "upload", "NameSet", "EntriesReceived", "receive_file_entries", "pack_names", "file_entries_stats",
+    "FilesServed", "serve_files_stats",
 ]
 
 
@@ -656,6 +657,36 @@ class EntriesReceived(NamedTuple):
     bad_name: Optional[int]
 
 
+class FilesServed(NamedTuple):
+    """What ``NameSet.serve_files`` returns (sf_serve_get_files_device):
+    ``run`` a ``wire.FilesRun`` holding the answers of requests ``[0,
+    n_answered)`` of the ``n_requests`` parsed; ``answered_bytes`` the bytes of
+    the request run those occupy; ``why`` what stopped the answering:
+    SF_SERVE_ALL, SF_SERVE_BAD_NAME (the next name is not UTF-8),
+    SF_SERVE_UNKNOWN (the set does not hold it) -- the caller sends the run and
+    raises "Bad filename encoding" / "Requested file is unknown", as the
+    reference does -- or SF_SERVE_FULL (the next answer would leave
+    ``max_run_bytes`` or 2^32 messages: send the run and call again with the
+    requests from ``answered_bytes`` on).  ``consumed`` / ``stop`` describe the
+    whole parsed prefix, as wire.parse_blocks_device."""
+    run: object
+    n_requests: int
+    n_answered: int
+    answered_bytes: int
+    why: int
+    consumed: int
+    stop: int
+
+
+def serve_files_stats() -> Tuple[int, int, int, int]:
+    """Test hook (sf_test_serve_files_stats): (route: 0 nothing launched, 1
+    parsed and no request answered, 2 a run built; requests; answered;
+    read-backs) of this process's last sf_serve_get_files_device."""
+    out = (ctypes.c_uint64 * 4)()
+    check(lib().sf_test_serve_files_stats(out), "sf_test_serve_files_stats")
+    return tuple(int(v) for v in out)
+
+
 def pack_names(names: Sequence[bytes], device=None) -> Tuple[torch.Tensor, torch.Tensor]:
     """A list of names as the library takes it: (packed bytes uint8, CSR
     int64[n + 1]) on ``device`` (``device_of``)."""
@@ -801,6 +832,45 @@ class NameSet:
                         have_hash_ok: Optional[torch.Tensor] = None) -> EntriesReceived:
         """``receive_file_entries`` of ``run`` against this set."""
         return receive_file_entries(run, self, have_hashes, have_hash_ok)
+
+    def serve_files(self, requests: torch.Tensor, file_first: torch.Tensor, digests: torch.Tensor,
+                    sizes: torch.Tensor, max_run_bytes: int = 0) -> FilesServed:
+        """The source's answer to a received run of GET_FILE requests, in one
+        call (sf_serve_get_files_device): ``requests`` (a flat uint8 HBM tensor)
+        is parsed as ``wire.Parser`` reads it, every name is looked up in this
+        set -- built over the source's non-temporary files in file_id order --
+        and request k becomes FILE_START with the name, one FILE_BLOCK per
+        block of its row and FILE_END.  ``file_first`` int64[rows + 1] is the
+        CSR of the set's rows into the block table ``digests`` uint8[n, 20] /
+        ``sizes`` int32/uint32[n] (row r owns blocks ``file_first[r] :
+        file_first[r + 1]``, in list_file_blocks order), all on the set's
+        device; nothing is gathered or copied per request.  ``max_run_bytes``
+        (0: no bound) bounds the run the call allocates.  See ``FilesServed``.
+        A row that answering reaches and whose CSR entries do not hold raises
+        ValueError naming it.  Blocking, for three read-backs."""
+        from .wire import FilesRun
+        dev = self.names.device
+        _require_device(requests, "requests", torch.uint8, dev)
+        _require_device(file_first, "file_first", torch.int64, dev)
+        n = _table20(digests, "digests", dev)
+        _list32(sizes, "sizes", n, dev)
+        if requests.dim() != 1 or file_first.dim() != 1 or file_first.numel() != self.n_rows + 1:
+            raise ValueError("requests must be flat and file_first hold one entry per row of the set and one more")
+        if not self._h:
+            raise ValueError("NameSet is closed")
+        h, stop, why = ctypes.c_void_p(), ctypes.c_int(0), ctypes.c_int(0)
+        nreq, nans, used, bad, consumed = (ctypes.c_uint64(0) for _ in range(5))
+        with _on(dev, self.stream):
+            rc = lib().sf_serve_get_files_device(self._h, file_first.data_ptr(), _ptr(digests, n), _ptr(sizes, n), n,
+                                                 _ptr(requests), requests.numel(), int(max_run_bytes), ctypes.byref(h),
+                                                 ctypes.byref(nreq), ctypes.byref(nans), ctypes.byref(used),
+                                                 ctypes.byref(why), ctypes.byref(bad), ctypes.byref(consumed),
+                                                 ctypes.byref(stop), _stream_ptr(self.names, self.stream))
+        if rc != 0 and bad.value != (1 << 64) - 1:
+            raise ValueError(f"row {bad.value}: its file_first entries do not hold")
+        check(rc, "sf_serve_get_files_device")
+        return FilesServed(FilesRun(h, dev, self.stream), nreq.value, nans.value, used.value, why.value,
+                           consumed.value, stop.value)
 
     def close(self) -> None:
         if self._h:

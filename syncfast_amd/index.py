@@ -760,6 +760,104 @@ class Index:
                                 packed, name_at.view(torch.int64))
         return run, len(files)
 
+    def source_tables(self, device=None) -> "SourceTables":
+        """The source's tables for ``serve_get_file_requests``, built once per
+        sync and kept in HBM: the packed names of all non-temporary files in
+        file_id order with their ``device.NameSet``, and the CSR ``file_first``
+        of those rows into one digest table and one size list holding every
+        file's ``list_file_blocks`` rows in that order -- all in one upload.
+        A small closeable object (``close()``, or a ``with`` block)."""
+        return SourceTables(self, device)
+
+    @staticmethod
+    def _get_files_on_host(data: bytes):
+        """The GET_FILE messages ``wire.Parser`` reads from byte 0 of ``data``
+        -> ([name], [end of each], consumed, stop): ``stop`` the SF_WIRE_* class
+        of what stands behind them."""
+        from . import wire
+        p = wire.Parser()
+        p._buf = bytearray(data)
+        names, ends, pos = [], [], 0
+        while True:
+            if pos == len(data):
+                return names, ends, pos, wire.SF_WIRE_END
+            try:
+                line = p._line(pos, wire.COMMAND_MAX, "Unterminated command")
+                if line is None:
+                    return names, ends, pos, wire.SF_WIRE_INCOMPLETE
+                if line[0] in (b"FILE_ENTRY", b"END_FILES", b"FILE_START", b"FILE_END", b"GET_BLOCK", b"FILE_BLOCK",
+                               b"BLOCK_DATA", b"COMPLETE"):  # another command's complete line, whatever follows it
+                    return names, ends, pos, wire.SF_WIRE_OTHER
+                r = p._one(pos)  # an unknown command raises
+            except wire.ProtocolError:
+                return names, ends, pos, wire.SF_WIRE_MALFORMED
+            if r is None:
+                return names, ends, pos, wire.SF_WIRE_INCOMPLETE
+            msg, pos = r
+            names.append(msg[1])
+            ends.append(pos)
+
+    def serve_get_file_requests(self, data, device=None, tables=None, max_run_bytes: int = 0):
+        """The source's ``Respond`` state for one received buffer of GET_FILE
+        requests (src/sync/fs.rs:177-231): the requests at the start of
+        ``data`` are parsed, each name resolved and answered with FILE_START,
+        its FILE_BLOCKs and FILE_END.  Returns (run, n_requests, n_answered,
+        answered_bytes, why, consumed, stop): ``consumed`` / ``stop`` describe
+        the parsed prefix as ``wire.parse_blocks_device`` does (a run that
+        arrives in pieces is continued with ``data[consumed:]`` + the new
+        bytes); ``run`` answers requests ``[0, n_answered)``, which occupy
+        ``data[:answered_bytes]``, and ``why`` says what stopped the answering:
+        wire.SF_SERVE_ALL, SF_SERVE_BAD_NAME, SF_SERVE_UNKNOWN -- the caller
+        sends the run and then raises "Bad filename encoding" / "Requested file
+        is unknown", as the reference does -- or SF_SERVE_FULL: with the next
+        answer the run would exceed ``max_run_bytes`` (0: no bound; a peer may
+        repeat one large file's name): send the run and call again with
+        ``data[answered_bytes:]``.
+
+        ``device=None`` is the definition: ``wire.Parser`` over ``data``, then
+        ``serve_get_files`` name by name; ``run`` is bytes.  With a device the
+        buffer goes up and ONE ``device.NameSet.serve_files`` call
+        (sf_serve_get_files_device) parses it, looks every name up and builds
+        the answer in HBM from ``tables`` (``source_tables(device)``: built here
+        and closed again when None -- keep one for the whole sync); ``run`` is
+        a ``wire.FilesRun``.  The device compares the received bytes with the
+        names as the index spells them, as the reference's query does; the
+        host route's ``get_file`` also finds a name that ``PurePath`` respells
+        (``a//b``).  The bound of 2^32 messages per run is the device route's
+        alone."""
+        from . import wire
+        data = bytes(data)
+        if device is not None or tables is not None:
+            from .device import upload
+            own = tables is None
+            t = self.source_tables(device) if own else tables
+            try:
+                got = t.name_set.serve_files(upload(data, t.device), t.file_first, t.digests, t.sizes,
+                                             max_run_bytes=max_run_bytes)
+            finally:
+                if own:
+                    t.close()
+            return tuple(got)
+        names, ends, consumed, stop = self._get_files_on_host(data)
+        out, answered, why = [], 0, wire.SF_SERVE_ALL
+        total = 0
+        for name in names:
+            try:
+                run, n = self.serve_get_files([name])
+            except wire.ProtocolError:
+                why = wire.SF_SERVE_BAD_NAME
+                break
+            if n == 0:
+                why = wire.SF_SERVE_UNKNOWN
+                break
+            if max_run_bytes and total + len(run) > max_run_bytes:
+                why = wire.SF_SERVE_FULL
+                break
+            out.append(run)
+            total += len(run)
+            answered += 1
+        return b"".join(out), len(names), answered, ends[answered - 1] if answered else 0, why, consumed, stop
+
     def file_entries(self, device=None):
         """The source's ``ListFiles`` state over ``list_files()``
         (src/sync/fs.rs:133-164): one FILE_ENTRY per file -- name, size,
@@ -1413,3 +1511,52 @@ class Index:
             if not (Path(path) / file_path).is_file():
                 log.info("Removing missing file %s", file_path)
                 self.remove_file(file_id)
+
+
+class SourceTables:
+    """What the source keeps in HBM while it answers GET_FILE requests
+    (``Index.source_tables``): ``names`` the names (bytes) of the index's
+    non-temporary files in file_id order, ``name_set`` the ``device.NameSet``
+    over them, ``file_first`` int64[rows + 1] the CSR of those rows into
+    ``digests`` uint8[n, 20] / ``sizes`` int32[n], which hold every file's
+    ``list_file_blocks`` rows in that order.  One upload; ``seconds`` says what
+    reading the database, packing and uploading, and building the set took.
+    ``close()`` frees the set (also on leaving a ``with`` block)."""
+
+    def __init__(self, index: "Index", device=None):
+        import time
+
+        import torch
+
+        from .device import NameSet, device_of, upload
+        t0 = time.perf_counter()
+        self.device = device_of(device)
+        files = index.db.execute("SELECT file_id, name FROM files WHERE temporary = 0 ORDER BY file_id;").fetchall()
+        self.names = [str(PurePath(r[1])).encode("utf-8") for r in files]
+        blocks = [index.list_file_blocks(int(r[0])) for r in files]
+        rows = [b for per_file in blocks for b in per_file]
+        t1 = time.perf_counter()
+        # one buffer, widest elements first so that every part starts on its own grid
+        parts = [np.cumsum([0] + [len(n) for n in self.names], dtype=np.int64).tobytes(),
+                 np.cumsum([0] + [len(b) for b in blocks], dtype=np.int64).tobytes(),
+                 np.fromiter((size for _h, _offset, size in rows), np.uint32, len(rows)).tobytes(),
+                 b"".join(h.bytes for h, _offset, _size in rows), b"".join(self.names)]
+        buf = upload(b"".join(parts), self.device)
+        at = np.cumsum([0] + [len(p) for p in parts]).tolist()
+        name_at, first, sizes, digests, packed = (buf[a:b] for a, b in zip(at, at[1:]))
+        self.file_first, self.sizes = first.view(torch.int64), sizes.view(torch.int32)
+        self.digests = digests.reshape(len(rows), 20)
+        torch.cuda.synchronize(self.device)
+        t2 = time.perf_counter()
+        self.name_set = NameSet(packed, name_at.view(torch.int64))
+        torch.cuda.synchronize(self.device)
+        self.seconds = {"database": t1 - t0, "pack_upload": t2 - t1, "name_set": time.perf_counter() - t2}
+
+    def close(self) -> None:
+        self.name_set.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()

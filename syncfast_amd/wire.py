@@ -21,6 +21,7 @@ from typing import List, Tuple
 
 from ._lib import (SF_ENOSPC, SF_OK, SF_WIRE_END, SF_WIRE_INCOMPLETE, SF_WIRE_MALFORMED,  # noqa: F401
                    SF_WIRE_END_FILES, SF_WIRE_OTHER, SF_WIRE_UNEXPECTED, check, lib)
+from ._lib import SF_SERVE_ALL, SF_SERVE_BAD_NAME, SF_SERVE_FULL, SF_SERVE_UNKNOWN  # noqa: F401
 from .digest import HashDigest
 
 
@@ -490,6 +491,38 @@ class GetFilesRun(BlockDataRun):
 
     def receive(self, *args, **kwargs):
         return Parser().receive(self.bytes())
+
+    def serve(self, name_set, file_first, digests, sizes, max_run_bytes: int = 0):
+        """The run handed straight to ``device.NameSet.serve_files``
+        (sf_serve_get_files_device) on the source's tables -- the source's half
+        of the exchange, what ``EntriesRun.receive`` is for the list -- and its
+        ``device.FilesServed``."""
+        return name_set.serve_files(self.tensor(), file_first, digests, sizes, max_run_bytes=max_run_bytes)
+
+
+def parse_get_files_device(run, stream=None):
+    """The inverse of ``get_files_device``: the GET_FILE messages at the start
+    of ``run``, a flat uint8 HBM tensor, parsed on the device
+    (sf_wire_parse_get_files_device) -> (name_at int64[n], name_len int32[n],
+    bad_name, consumed, stop).  The n requests are exactly those ``Parser``
+    reads from byte 0 until something else stands there; request i's name is
+    ``run[name_at[i] : + name_len[i]]`` -- the spans ``device.NameSet.lookup``
+    takes -- ``bad_name`` the first request whose name is not UTF-8, or None;
+    ``consumed`` / ``stop`` as ``parse_blocks_device``.  Blocking."""
+    torch, dev = _device(run, "run")
+    if run.dim() != 1:
+        raise ValueError("run must be a flat uint8 tensor")
+    n, bad, consumed, stop = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_int(0)
+    cap = run.numel() // 10 + 1  # a request is at least 10 bytes
+    with dev._on(run.device, stream):
+        name_at = torch.empty(cap, dtype=torch.int64, device=run.device)
+        name_len = torch.empty(cap, dtype=torch.int32, device=run.device)
+        check(lib().sf_wire_parse_get_files_device(dev._ptr(run), run.numel(), name_at.data_ptr(), name_len.data_ptr(),
+                                                   cap, ctypes.byref(n), ctypes.byref(bad), ctypes.byref(consumed),
+                                                   ctypes.byref(stop), _stream(torch, run)),
+              "sf_wire_parse_get_files_device")
+    return (name_at[:n.value], name_len[:n.value], None if bad.value == (1 << 64) - 1 else bad.value, consumed.value,
+            stop.value)
 
 
 def file_entries_device(names, name_at, sizes, hashes, end_files: bool = True, stream=None) -> EntriesRun:
