@@ -1283,6 +1283,91 @@ int sf_index_device_zpaq(const void *d_data, uint64_t len, uint32_t bits, uint32
 int sf_index_fd_zpaq(int fd, const sf_file_stamp *expect, uint32_t bits, uint32_t max_size,
                      sf_block_sig **rows, uint64_t *n_out, uint8_t blocks_hash[SF_HASH_DIGEST_LEN]);
 
+/* sf_cut_device_zpaq over MANY files of one buffer in HBM, in one call: file f
+ * is bytes d_data[file_offsets[f], + file_lens[f]) (HOST arrays of n_files
+ * entries; files need no alignment and may abut, leave gaps or overlap), and
+ * every file is cut from a fresh chunker, as a file of its own.  The rows of
+ * all files come out in file order -- d_offsets are positions in d_data, so
+ * the list is exactly what sf_index_device_blocks takes -- and
+ * d_first_row[f] (n_files + 1 entries) is the row where file f starts.  The
+ * segments of all files fill the lanes together (sf_cdc_files.hip): a batch of
+ * small files is cut like one huge one, with no join across files.
+ *
+ * max_rounds bounds the join launches (0 = no bound).  A file that still cut
+ * again in the last launch made is UNSETTLED: it has no rows
+ * (d_first_row[f] == d_first_row[f + 1]), unsettled[f] = 1 (HOST, n_files
+ * bytes, may be NULL; 0 for every other file) and *n_unsettled (may be NULL)
+ * counts such files.  When the bound was reached these are exactly the files
+ * that need at least max_rounds rounds (constant or periodic data: one round
+ * per segment); when the joins ended by themselves there is none.  For every
+ * settled file the rows minus file_offsets[f] are sf_zpaq_cut_buffer's list of
+ * the file's bytes, for any input.
+ *
+ * BLOCKING: `stream` is synchronised once per join launch and once for the
+ * count.  *n_blocks = the rows of the settled files; SF_ENOSPC (no device
+ * output written) when cap_blocks is smaller or a device output is NULL.
+ * n_files == 0, or every file empty: SF_OK, 0 blocks, d_first_row (when given)
+ * all zeros.  SF_ERANGE with *bad_file (may be NULL) = the first file that does
+ * not lie in d_data[0, data_len).  SF_EINVAL for bits / max_size outside
+ * sf_cut_device_zpaq's range or a misaligned output: d_offsets and
+ * d_first_row 8-B aligned, d_sizes 4-B aligned.  Both are returned before any
+ * device call.  Scratch, from the library's stream-ordered pool: two bitmaps
+ * of sum ceil(len_f / 32) words, 56 bytes per segment, 36 bytes per file. */
+int sf_cut_device_zpaq_files(const void *d_data, uint64_t data_len, const uint64_t *file_offsets,
+                             const uint64_t *file_lens, uint32_t n_files, uint32_t bits, uint32_t max_size,
+                             uint32_t max_rounds, uint64_t *d_offsets, uint32_t *d_sizes, uint64_t cap_blocks,
+                             uint64_t *d_first_row, uint64_t *n_blocks, uint8_t *unsettled,
+                             uint32_t *n_unsettled, uint32_t *bad_file, void *stream);
+
+/* The many-file form of sf_index_device_zpaq: sf_cut_device_zpaq_files, then
+ * the explicit-list kernel over the whole list into d_digests
+ * (cap_blocks x 20 B, 4-B aligned; with SF_ENOSPC no digest is written
+ * either, and a NULL d_digests is SF_ENOSPC like any other missing output).
+ * If blocks_hashes (HOST, 20 x n_files bytes, may be NULL) is given, the
+ * digests are copied back and every file's blocks_hash is chained on the
+ * host: SHA-1("") for a file with no blocks, 20 zero bytes for an unsettled
+ * file.  Blocking and errors as sf_cut_device_zpaq_files. */
+int sf_index_device_zpaq_files(const void *d_data, uint64_t data_len, const uint64_t *file_offsets,
+                               const uint64_t *file_lens, uint32_t n_files, uint32_t bits, uint32_t max_size,
+                               uint32_t max_rounds, uint64_t *d_offsets, uint32_t *d_sizes, void *d_digests,
+                               uint64_t cap_blocks, uint64_t *d_first_row, uint64_t *n_blocks,
+                               uint8_t *blocks_hashes, uint8_t *unsettled, uint32_t *n_unsettled,
+                               uint32_t *bad_file, void *stream);
+
+/* index_path's default mode (src/index.rs:685-715 over 610-659) for many
+ * regular files open on fds[0 .. n_files), with no host chunker and no lists
+ * handed in: sf_index_fds_blocks without its second read.  Each file is read
+ * ONCE, with pread by the library's reader threads, into packed pinned stages
+ * of about stage_bytes (0 = 256 MiB; each file at a 64-byte boundary of its
+ * stage); per stage one H2D copy, one many-file cut
+ * (sf_cut_device_zpaq_files, at most max_rounds join launches, 0 = no bound),
+ * one explicit-list launch over every block of the stage and one D2H of list
+ * and digests.  Stage k's copy and the first, largest part of its cut run
+ * while stage k + 1 is read.  A file that did not settle under max_rounds is
+ * finished inside the call: it is cut by the host cutter
+ * (sf_zpaq_cut_buffer's code, on the reader threads, one file per thread) from
+ * the stage's pinned bytes and hashed by a second launch over the same stage
+ * in HBM -- the result is complete and exact whatever max_rounds is.  A file
+ * larger than a stage goes through sf_index_fd_zpaq's windows, in its place in
+ * the file order.
+ *
+ * *rows (allocated by the library, *n_out entries, release with sf_free_rows;
+ * also set when the call returns a file's own failure) holds file 0's rows,
+ * then file 1's, ...: file f's are [first_row[f], first_row[f + 1])
+ * (n_files + 1 entries), offsets relative to the file.  blocks_hashes
+ * (20 x n_files): every file's blocks_hash, SHA-1("") for an empty file.
+ * stamps (may be NULL), file_status (may be NULL) and bad_file as in
+ * sf_index_fds_blocks: each file succeeds or fails alone -- SF_EINVAL for a
+ * descriptor that is not a regular file, SF_EAGAIN when its stamp differs from
+ * stamps[f] or moved while it was read, SF_EIO -- a failed file has no rows
+ * and a zeroed blocks_hash, and the call returns the first failing file's
+ * code with *bad_file naming it.  SF_EINVAL for bits / max_size outside
+ * sf_cut_device_zpaq's range.  n_files == 0 needs no device.  Blocking. */
+int sf_index_fds_zpaq(const int *fds, const sf_file_stamp *stamps, uint32_t n_files, uint32_t bits,
+                      uint32_t max_size, uint32_t max_rounds, uint64_t stage_bytes, sf_block_sig **rows,
+                      uint64_t *n_out, uint64_t *first_row, uint8_t *blocks_hashes, int *file_status,
+                      uint32_t *bad_file);
+
 /* ------------------------------------------- one process, N devices ---- */
 
 /* Contiguous, block-aligned shard `shard` of n_shards of a file_len-byte file:

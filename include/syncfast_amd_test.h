@@ -81,6 +81,16 @@ int sf_test_xcd_litmus(int mode, uint32_t out[8]);
  * them.  Host only; not synchronised with cuts in flight. */
 int sf_test_zpaq_device_stats(uint64_t out[4]);
 
+/* What the many-file device ZPAQ cutter (sf_cut_device_zpaq_files and the
+ * calls built on it) did in its most recent call in this process: out[0] the
+ * segment length in bytes, out[1] the segments of all files, out[2] the join
+ * launches made (one more than the rounds in which a segment cut again when
+ * the joins ended by themselves; max_rounds when the bound was reached; 0
+ * when no file has two segments), out[3] the bytes cut again in all of them,
+ * out[4] the unsettled files, out[5] the files finished on the host (0 for
+ * the calls over HBM).  Host only; not synchronised with cuts in flight. */
+int sf_test_zpaq_files_stats(uint64_t out[6]);
+
 /* What the last FILE_BLOCK parse of this process did (sf_wire_parse_blocks_device
  * and the calls built on it): out[0] the candidate positions the device found
  * (0 when the parse was forced to the host), out[1] the messages, out[2] 1 if

@@ -170,6 +170,11 @@ def _table():
         "sf_cut_device_zpaq": (i32, [vp, u64, u32, u32, vp, vp, u64, pu64, vp]),
         "sf_index_device_zpaq": (i32, [vp, u64, u32, u32, vp, vp, vp, u64, pu64, vp, vp]),
         "sf_index_fd_zpaq": (i32, [i32, vp, u32, u32, P(sig), pu64, vp]),
+        "sf_cut_device_zpaq_files": (i32, [vp, u64, vp, vp, u32, u32, u32, u32, vp, vp, u64, vp, pu64, vp, pu32, pu32,
+                                           vp]),
+        "sf_index_device_zpaq_files": (i32, [vp, u64, vp, vp, u32, u32, u32, u32, vp, vp, vp, u64, vp, pu64, vp, vp, pu32,
+                                             pu32, vp]),
+        "sf_index_fds_zpaq": (i32, [vp, vp, u32, u32, u32, u32, u64, P(sig), pu64, pu64, vp, vp, pu32]),
         "sf_shard_range": (i32, [u64, u32, u32, u32, pu64, pu64]),
         "sf_index_file_multi": (i32, [cp, u32, u32, sig, u64, pu64, vp]),
         "sf_index_device_multi": (i32, [u32, vp, u64, u32, vp, u32, vp, vp]),
@@ -190,6 +195,7 @@ def _table():
         "sf_test_multi_plan": (i32, [u64, u32, u32, u32, i32, vp, vp, vp]),
         "sf_test_xcd_litmus": (i32, [i32, pu32]),
         "sf_test_zpaq_device_stats": (i32, [vp]),
+        "sf_test_zpaq_files_stats": (i32, [vp]),
         "sf_test_wire_parse_stats": (i32, [vp]),
         "sf_test_recv_files_stats": (i32, [vp]),
         "sf_test_file_entries_stats": (i32, [vp]),

@@ -31,6 +31,9 @@
 //   sf_pool.cpp   the host worker threads of every pipeline (run_pool);
 //   sf_zpaq.cpp   the reference's ZPAQ chunker on the host;
 //   sf_cdc.hip    the same boundaries cut on the device (its own kernels);
+//   sf_cdc_files.hip  the same for many files of one buffer in one call (its
+//                 own kernels; the lane code is sf_cdc_lane.hpp, shared with
+//                 sf_cdc.hip; the geometry is sf_cdc_files_plan.hpp);
 //   sf_recv.hip   FILE_BLOCK runs parsed on the device (its own kernels; the
 //                 host parser is sf_wire_parse.hpp);
 //   sf_recv_data.hip  BLOCK_DATA runs parsed and their payloads verified on
@@ -400,5 +403,40 @@ int zpaq_check_device_params(uint32_t bits, uint32_t max_size);
 int zpaq_cut_plan(const uint8_t* d_data, uint64_t len, uint32_t bits, uint32_t max_size, hipStream_t s, ZpaqPlan* p);
 int zpaq_cut_emit(const ZpaqPlan& p, uint64_t* d_offsets, uint32_t* d_sizes, hipStream_t s);
 void zpaq_cut_free(ZpaqPlan* p, hipStream_t s);
+// The windows of sf_index_fd_zpaq over the `len` bytes of the regular file
+// open on fd: the rows (file offsets) appended to rb, folded into bh.
+int fd_zpaq_windows(int fd, uint64_t len, uint32_t bits, uint32_t max_size, RowBuf& rb, sf_host_sha1_stream* bh);
+
+// The same over many files of one buffer (sf_cdc_files.hip; the geometry is
+// sf_cdc_files_plan.hpp).  zpaq_files_check: every file lies in the buffer, or
+// SF_ERANGE and *bad_file.  A plan is the cut of the checked files (at least
+// one not empty) up to the count, in two parts: zpaq_files_begin allocates,
+// uploads the per-file arrays (`host`: it lives until `synced`, or until the
+// stream has been synchronised) and launches round 0, asynchronously;
+// zpaq_files_finish makes at most max_rounds join launches (0 = no cap) and
+// counts, blocking as zpaq_cut_plan: `total` rows of the settled files,
+// unsettled[f] = 1 for the others.  zpaq_files_emit writes the rows and
+// first_row[0 .. n_files] (asynchronous).
+struct ZpaqFilesPlan {
+  void* ws = nullptr;
+  uint64_t L = 0, nseg = 0, total = 0, most = 0, recut = 0;
+  uint32_t n_files = 0, launches = 0, n_unsettled = 0, bits = 0, max_size = 0;
+  bool synced = false;
+  const void* d_data = nullptr;
+  void *spec = nullptr, *cur = nullptr, *seg[6] = {}, *ctr = nullptr, *d_files = nullptr, *round = nullptr,
+       *scan_tmp = nullptr;
+  size_t scan_bytes = 0;
+  const void *ends = nullptr, *last = nullptr;
+  std::vector<uint64_t> host;
+  std::vector<uint8_t> unsettled;
+};
+int zpaq_files_check(uint64_t data_len, const uint64_t* offs, const uint64_t* lens, uint32_t n, uint32_t* bad_file);
+int zpaq_files_begin(const uint8_t* d_data, const uint64_t* offs, const uint64_t* lens, uint32_t n, uint32_t bits,
+                     uint32_t max_size, hipStream_t s, ZpaqFilesPlan* p);
+int zpaq_files_finish(ZpaqFilesPlan* p, uint32_t max_rounds, hipStream_t s);
+int zpaq_files_emit(const ZpaqFilesPlan& p, uint64_t* d_offsets, uint32_t* d_sizes, uint64_t* d_first_row,
+                    hipStream_t s);
+void zpaq_files_free(ZpaqFilesPlan* p, hipStream_t s);
+void zpaq_files_stat(int k, uint64_t v);  // field k of sf_test_zpaq_files_stats
 
 }  // namespace sfi

@@ -14,6 +14,8 @@ Reference mapping (/root/reference):
   cut_device_zpaq       -> the reference's own chunker (cdchunking's ZPAQ,
                            src/index.rs:622-625) cut on the device
   index_device_zpaq     -> index_file's default mode end to end in HBM
+  cut_zpaq_files / index_zpaq_files -> the same for many files of one buffer
+                           in one call (index_path_rec's default mode)
 """
 from __future__ import annotations
 
@@ -32,6 +34,7 @@ __all__ = [
     "index_device_weak", "index_device_blocks_weak", "BatchStream",
     "fill_splitmix", "splitmix_tensor", "BlockSet", "index_device_multi",
     "cut_device_zpaq", "index_device_zpaq", "zpaq_segment_len", "zpaq_device_stats",
+    "cut_zpaq_files", "index_zpaq_files", "zpaq_files_stats", "ZpaqFiles",
     "copy_blocks", "copy_stats", "write_to_fd", "get_block_requests", "place_block_data",
     "device_of", "upload", "NameSet", "EntriesReceived", "receive_file_entries", "pack_names", "file_entries_stats",
     "FilesServed", "serve_files_stats",
@@ -238,6 +241,86 @@ def index_device_zpaq(data: torch.Tensor, bits: int = 13, max_size: int = 32768,
     Returns (offsets int64[n], sizes int32[n], digests uint8[n, 20],
     blocks_hash or None)."""
     return _zpaq_call(data, bits, max_size, stream, True, blocks_hash)
+
+
+class ZpaqFiles(NamedTuple):
+    """What cut_zpaq_files / index_zpaq_files return: the rows of every
+    settled file in file order (offsets are positions in the buffer),
+    first_row int64[n_files + 1] on the device, unsettled bool[n_files] on the
+    host, and for the index form digests uint8[n, 20] and, when asked for,
+    blocks_hashes uint8[n_files, 20] on the host (zeros for an unsettled
+    file)."""
+    offsets: torch.Tensor
+    sizes: torch.Tensor
+    first_row: torch.Tensor
+    unsettled: np.ndarray
+    digests: Optional[torch.Tensor]
+    blocks_hashes: Optional[np.ndarray]
+
+
+def zpaq_files_stats() -> Tuple[int, int, int, int, int, int]:
+    """(segment length, segments, join launches, bytes cut again, unsettled
+    files, files finished on the host) of the most recent many-file device cut
+    in this process (sf_test_zpaq_files_stats)."""
+    out = (ctypes.c_uint64 * 6)()
+    check(lib().sf_test_zpaq_files_stats(out), "sf_test_zpaq_files_stats")
+    return tuple(int(v) for v in out)
+
+
+def _zpaq_files_call(data, files, bits, max_size, max_rounds, stream, digests: bool, blocks_hashes: bool) -> ZpaqFiles:
+    """sf_cut_device_zpaq_files / sf_index_device_zpaq_files with outputs
+    sized from a guess and once more from the need the library reports with
+    SF_ENOSPC (as _zpaq_call)."""
+    _require_device(data, "data", torch.uint8)
+    fa = np.ascontiguousarray(np.asarray(files, dtype=np.uint64).reshape(-1, 2))
+    nf = fa.shape[0]
+    offs_h, lens_h = np.ascontiguousarray(fa[:, 0]), np.ascontiguousarray(fa[:, 1])
+    total = int(lens_h.sum())
+    name = "sf_index_device_zpaq_files" if digests else "sf_cut_device_zpaq_files"
+    mask = np.zeros(nf, np.uint8)
+    bh = np.zeros((nf, 20), np.uint8) if blocks_hashes else None
+    nb, nu, bad = ctypes.c_uint64(0), ctypes.c_uint32(0), ctypes.c_uint32(0)
+
+    def call(cap):
+        offs = torch.empty(cap, dtype=torch.int64, device=data.device)
+        sizes = torch.empty(cap, dtype=torch.int32, device=data.device)
+        first = torch.empty(nf + 1, dtype=torch.int64, device=data.device)
+        dig = torch.empty((cap, 20), dtype=torch.uint8, device=data.device) if digests else None
+        head = (_ptr(data), data.numel(), offs_h.ctypes.data, lens_h.ctypes.data, nf, bits, max_size, max_rounds,
+                _ptr(offs), _ptr(sizes))
+        tail = (mask.ctypes.data, ctypes.byref(nu), ctypes.byref(bad), _stream_ptr(data, stream))
+        if digests:
+            rc = lib().sf_index_device_zpaq_files(*head, _ptr(dig), cap, _ptr(first), ctypes.byref(nb),
+                                                  bh.ctypes.data if blocks_hashes else None, *tail)
+        else:
+            rc = lib().sf_cut_device_zpaq_files(*head, cap, _ptr(first), ctypes.byref(nb), *tail)
+        return rc, nb.value, (offs, sizes, first, dig)
+    with _on(data.device, stream):
+        k, (offs, sizes, first, dig) = retry_enospc(
+            call, (total >> max(bits - 1, 0)) + total // max_size + nf + 16, 2,
+            lambda rc: f"{name}: file {bad.value}" if rc == SF_ERANGE else name)
+    return ZpaqFiles(offs[:k], sizes[:k], first, mask.astype(bool), dig[:k] if digests else None, bh)
+
+
+def cut_zpaq_files(data: torch.Tensor, files, bits: int = 13, max_size: int = 32768, max_rounds: int = 0,
+                   stream: Optional[torch.cuda.Stream] = None) -> ZpaqFiles:
+    """cut_device_zpaq for many files of one HBM buffer in one call
+    (sf_cut_device_zpaq_files): ``files`` is a sequence of (offset, length);
+    every file is cut as a file of its own, and the segments of all of them
+    fill the device together.  ``max_rounds`` bounds the join launches
+    (0: none); a file that has not settled by then has no rows and is marked
+    in ``unsettled``.  Blocking: the stream is synchronised once per join
+    launch."""
+    return _zpaq_files_call(data, files, bits, max_size, max_rounds, stream, False, False)
+
+
+def index_zpaq_files(data: torch.Tensor, files, bits: int = 13, max_size: int = 32768, max_rounds: int = 0,
+                     blocks_hashes: bool = True, stream: Optional[torch.cuda.Stream] = None) -> ZpaqFiles:
+    """index_zpaq for many files of one HBM buffer (sf_index_device_zpaq_files):
+    cut_zpaq_files, every block's SHA-1 and, with ``blocks_hashes``, every
+    file's blocks_hash (chained on the host; SHA-1("") for a file with no
+    blocks, zeros for an unsettled one)."""
+    return _zpaq_files_call(data, files, bits, max_size, max_rounds, stream, True, blocks_hashes)
 
 
 def index_device_batch(data: torch.Tensor, files: Sequence[Tuple[int, int]], block_size: int,

@@ -266,13 +266,19 @@ class ZpaqChunker(NativeChunker):
     the GPU as well: Index.index_file, and index_path's large-file route, go
     through sf_index_fd_zpaq (the file read once, cut and hashed in HBM by
     windows) instead of sf_index_fd_cut's host threads; the rows are the
-    same.  The default stays on the host route: it is the faster one up to
-    about 1 GiB (DESIGN.md 3.7 has the measurements)."""
+    same.  With ``device=True`` index_path's smaller files are not cut on
+    the host either: each batch goes through one sf_index_fds_zpaq call (every
+    file read once, a whole stage of files cut on the device at a time;
+    ``max_rounds`` bounds a stage's join launches, and a file that has not
+    settled by then is finished by the host cutter inside the call).  The
+    default stays on the host route (DESIGN.md 3.7 and 3.17 have the
+    measurements)."""
 
-    def __init__(self, bits: int = 13, max_size: int = 32768, device: bool = False, threads: int = 0):
+    def __init__(self, bits: int = 13, max_size: int = 32768, device: bool = False, threads: int = 0,
+                 max_rounds: int = host.ZPAQ_MAX_ROUNDS):
         self._zops = host.ZpaqOps(bits, max_size)  # kept alive: ops is its address
         super().__init__(self._zops.address, threads)
-        self.bits, self.max_size, self.device = bits, max_size, device
+        self.bits, self.max_size, self.device, self.max_rounds = bits, max_size, device, max_rounds
 
     def index_fd(self, fd: int, threads: int, stamp):
         """(rows, blocks_hash) of the regular file open on fd, cut and hashed
@@ -1380,7 +1386,12 @@ class Index:
         (streamed, as index_file streams it) and, with a NativeChunker, a
         regular file of at least `large_file_bytes` (cut on the chunker's
         threads and hashed from one read, sf_index_fd_cut, with the stamp
-        taken at its open)."""
+        taken at its open).
+
+        With ZpaqChunker(device=True) the batched files are not cut here at
+        all: they are stamped and collected, and each batch goes through one
+        sf_index_fds_zpaq call, which reads every file once and cuts and
+        hashes it on the device.  Everything else is as above."""
         import resource
         from concurrent.futures import ThreadPoolExecutor
 
@@ -1389,17 +1400,23 @@ class Index:
         soft = resource.getrlimit(resource.RLIMIT_NOFILE)[0]
         max_files = max(16, min(4096, (soft if soft > 0 else 1024) // 4))
         native = isinstance(ch, NativeChunker)
+        on_device = isinstance(ch, ZpaqChunker) and ch.device  # the batches are cut by sf_index_fds_zpaq
 
         def finish(batch):
             """Hash the cut files of `batch` in one call, close them, store them."""
             entries = batch.entries
             if not entries:
                 return
-            cuts = [e[5].result() for e in entries]
-            keep = [k for k, c in enumerate(cuts) if c is not None]
-            lists = [(_offsets(cuts[k]), np.asarray(cuts[k], np.uint32)) for k in keep]
-            res = host.index_fds_blocks([entries[k][3].fileno() for k in keep], lists,
-                                        [entries[k][4] for k in keep], stage_bytes=batch_bytes) if keep else None
+            if on_device:
+                keep = list(range(len(entries)))
+                res = host.index_fds_zpaq([e[3].fileno() for e in entries], ch.bits, ch.max_size,
+                                          [e[4] for e in entries], ch.max_rounds, batch_bytes)
+            else:
+                cuts = [e[5].result() for e in entries]
+                keep = [k for k, c in enumerate(cuts) if c is not None]
+                lists = [(_offsets(cuts[k]), np.asarray(cuts[k], np.uint32)) for k in keep]
+                res = host.index_fds_blocks([entries[k][3].fileno() for k in keep], lists,
+                                            [entries[k][4] for k in keep], stage_bytes=batch_bytes) if keep else None
             batch.close()  # cut and hashed: nothing reads its descriptors any more
             pos = {k: j for j, k in enumerate(keep)}
             for k, (fid, p, rel, _f, _st, _fut) in enumerate(entries):
@@ -1446,7 +1463,8 @@ class Index:
                             changed = True
                     else:
                         cutting.enter_context(mine.pop_all())
-                        cutting.entries.append((file_id, p, rel, f, stamp, pool.submit(_cut_stamped, ch.fn, f, stamp)))
+                        cut = None if on_device else pool.submit(_cut_stamped, ch.fn, f, stamp)
+                        cutting.entries.append((file_id, p, rel, f, stamp, cut))
                         cutting.nbytes += stamp.size
                 if changed:
                     self._index_file_retrying(p, rel, changed=True)
