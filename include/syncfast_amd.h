@@ -982,6 +982,92 @@ int sf_copy_blocks_device(const void *d_src, uint64_t src_len, void *d_dst, uint
 int sf_write_device_fd(const void *d_data, uint64_t len, int fd, uint64_t file_offset,
                        uint64_t *n_written, void *stream);
 
+/* The local half of the GetFiles state in one call: the outputs of
+ * sf_receive_files_device become the copy list sf_copy_blocks_device takes and
+ * the row arrays sf_wire_get_blocks_device (d_ask is its d_take) and
+ * sf_place_block_data_device (d_present, d_dst are its d_row_present,
+ * d_row_dst) take, with no host pass over the blocks.  The reference copies
+ * every block get_block finds, on trust (read_block + write_block,
+ * fs.rs:463-470); here a local block is hashed and compared with the digest
+ * the source announced before it is used, so a file edited after it was
+ * indexed costs a request, not a wrong image.
+ *
+ * Blocks (n_blocks entries each, as sf_receive_files_device wrote them):
+ * d_digests, d_sizes, d_offsets, d_rows and d_block_file; d_file_base[f] is
+ * where byte 0 of section f lies in the image allocation.  The table the block
+ * set was built from, in rowid order (n_table entries each): d_table_file[r]
+ * the local file that holds row r, in the caller's numbering, d_table_offset[r]
+ * and d_table_size[r] the row's place in it.  Local files (n_local entries
+ * each): d_local_size[j] the file's size now, d_local_base[j] where its byte 0
+ * lies in the arena d_src[0, src_len), or UINT64_MAX for a file that is not
+ * loaded.
+ *
+ * Block i with r = d_rows[i] and j = d_table_file[r] gets the first class that
+ * applies:
+ *   missing        r < 0
+ *   size mismatch  d_table_size[r] != d_sizes[i] (the reference would copy the
+ *                  chunk it cuts again at that offset; a job longer than its
+ *                  block would overlap the next block's range)
+ *   stale          d_table_offset[r] + d_sizes[i] > d_local_size[j]
+ *   unavailable    d_local_base[j] == UINT64_MAX
+ *   empty          d_sizes[i] == 0: present, and no job
+ *   candidate      everything else.
+ * With d_src the candidates' bytes, d_src[d_local_base[j] + d_table_offset[r],
+ * + d_sizes[i]), are hashed by the explicit-list kernel, as a list of the
+ * candidates alone; a candidate whose digest is d_digests[20 i, + 20) is a
+ * job, any other is unverified.  With d_src NULL every candidate is a job.
+ *
+ * For every block: d_dst[i] = d_file_base[d_block_file[i]] + d_offsets[i],
+ * d_present[i] = 1 for a job and an empty block, else 0, d_ask[i] =
+ * !d_present[i].  The jobs, numbered in block order: d_src_offsets[k],
+ * d_dst_offsets[k], d_job_sizes[k] and d_job_blocks[k] = i.  Blocks tile their
+ * sections, so the first counts[SF_PLAN_JOBS] entries are one
+ * sf_copy_blocks_device call with no sort.  d_local_jobs[j] (may be NULL) =
+ * the jobs that read local file j.  counts (host, SF_PLAN_COUNTS entries):
+ * the SF_PLAN_* numbers below.
+ *
+ * A query -- d_local_base or one of the four job lists NULL -- and a call
+ * whose cap is below the job count return SF_ENOSPC with counts filled and
+ * d_local_jobs written, and nothing else of the caller's is written (the
+ * per-block outputs may be NULL in a query).  d_local_jobs is the query's
+ * answer: which local files to load.  With d_local_base NULL no file is
+ * unavailable and nothing is verified: a candidate counts as a job.
+ *
+ * SF_ERANGE, with nothing written and counts untouched, when any block has
+ * r >= n_table, d_table_file[r] >= n_local, d_block_file[i] >= n_files, a
+ * destination sum past 2^64 - 1 or, with d_src, a candidate outside
+ * [0, src_len).  SF_EINVAL, before any device call, for a NULL input list
+ * with entries to read, a NULL per-block output outside a query, a list off
+ * its alignment (4 B: d_digests, d_sizes, d_block_file, d_table_file,
+ * d_table_size, d_job_sizes, d_local_jobs; 8 B: the 64-bit lists), a count
+ * above 2^31 or a NULL counts.  n_blocks == 0 launches nothing but the
+ * clearing of d_local_jobs (no device call at all when that is NULL).
+ *
+ * Blocking: one read-back without verification (the candidate count), two
+ * with it (then the job count).  Scratch: 9 n_blocks bytes, 32 per candidate
+ * and the scan's, from the library's stream-ordered pool (sf_plan_copies.hip,
+ * DESIGN.md 3.18). */
+#define SF_PLAN_JOBS 0          /* blocks copied from local files */
+#define SF_PLAN_BYTES 1         /* their bytes */
+#define SF_PLAN_MISSING 2
+#define SF_PLAN_SIZE_MISMATCH 3
+#define SF_PLAN_STALE 4
+#define SF_PLAN_UNAVAILABLE 5
+#define SF_PLAN_UNVERIFIED 6
+#define SF_PLAN_EMPTY 7
+#define SF_PLAN_COUNTS 8
+int sf_plan_copies_device(const void *d_digests /* 4-B aligned */, const uint32_t *d_sizes,
+                          const uint64_t *d_offsets, const int64_t *d_rows, const uint32_t *d_block_file,
+                          uint64_t n_blocks, const uint64_t *d_file_base, uint64_t n_files,
+                          const uint32_t *d_table_file, const uint64_t *d_table_offset,
+                          const uint32_t *d_table_size, uint64_t n_table,
+                          const uint64_t *d_local_base /* NULL: a query */, const uint64_t *d_local_size,
+                          uint64_t n_local, const void *d_src /* NULL: no verification */, uint64_t src_len,
+                          uint8_t *d_present, uint8_t *d_ask, uint64_t *d_dst, uint64_t *d_src_offsets,
+                          uint64_t *d_dst_offsets, uint32_t *d_job_sizes, int64_t *d_job_blocks, uint64_t cap,
+                          uint32_t *d_local_jobs /* may be NULL */,
+                          uint64_t *counts /* host: SF_PLAN_COUNTS entries */, void *stream);
+
 /* Deterministic synthetic input (bench / tests): bytes [start, start+len)
  * of the splitmix64 stream with this seed.  d_out needs no
  * alignment (16-B stores when d_out and start are 16-B aligned, else bytes). */
@@ -1045,6 +1131,22 @@ typedef struct sf_file_stamp {
 
 /* fstat(fd) as a stamp.  SF_EIO if fstat fails. */
 int sf_file_stamp_fd(int fd, sf_file_stamp *out);
+
+/* The loader of the destination's local files, the twin of
+ * sf_write_device_fd: bytes [file_offset, + len) of fd go to d_dst[0, len).
+ * They are read with pread (the position is not used or moved), in slices by
+ * the library's reader threads, into two pinned stages (64 MiB) and copied to
+ * the device stage by stage on `stream`, after what it holds at the call;
+ * stage k is read while stage k - 1 is copied.  *n_read (may be NULL) = the
+ * bytes of the whole stages known copied.  `expect` (may be NULL) is the stamp
+ * the caller took of the file: SF_EAGAIN when the file's stamp is another
+ * before the read or has moved after it -- d_dst[0, len) is then unspecified,
+ * and nothing outside it is touched.  SF_EIO for a file shorter than
+ * file_offset + len, SF_EINVAL, before any device call, for fd < 0, a
+ * descriptor that cannot seek (a pipe) or a NULL d_dst with len > 0.
+ * Blocking; launches no kernel. */
+int sf_read_fd_device(int fd, const sf_file_stamp *expect /* may be NULL */, uint64_t file_offset,
+                      uint64_t len, void *d_dst, uint64_t *n_read /* may be NULL */, void *stream);
 
 /* The explicit list over the regular file OPEN on fd -- the handle the caller's
  * chunker just streamed (index_file opens the file once and takes the mtime,

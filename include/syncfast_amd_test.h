@@ -141,6 +141,13 @@ int sf_test_block_data_stats(uint64_t out[4]);
  * threads. */
 int sf_test_copy_stats(uint64_t out[4]);
 
+/* What the last sf_plan_copies_device of this process did: out[0] the
+ * read-backs (synchronisations of the call: 1 without verification or without
+ * a candidate, 2 with both; 0 when nothing was launched), out[1] the
+ * candidates hashed (0 without verification), out[2] the jobs, out[3] 1 for a
+ * query.  Host only; not synchronised with calls in flight. */
+int sf_test_plan_copies_stats(uint64_t out[4]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,7 +15,8 @@ Modules
   wire    -- FILE_BLOCK / FILE_ENTRY framing (src/sync/ssh/proto.rs) and the
              device-built FILE_BLOCK run
   assemble -- the incoming files of a sync as HBM images: the copy and write
-             lists of the sink carried out by the block copy kernel
+             lists of the sink carried out by the block copy kernel, and the
+             local files a copy plan reads as one HBM arena
 """
 from ._lib import (HASH_DIGEST_LEN, LIB_PATH, MAX_BLOCK_SIZE, SfError, device_count,  # noqa: F401
                    lib)

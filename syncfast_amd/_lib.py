@@ -149,11 +149,14 @@ def _table():
                                             pu64, pu64, pu64, vp]),
         "sf_copy_blocks_device": (i32, [vp, u64, vp, u64, vp, vp, vp, vp, u64, vp, vp]),
         "sf_write_device_fd": (i32, [vp, u64, i32, u64, pu64, vp]),
+        "sf_plan_copies_device": (i32, [vp, vp, vp, vp, vp, u64, vp, u64, vp, vp, vp, u64, vp, vp, u64, vp, u64, vp, vp, vp,
+                                       vp, vp, vp, vp, u64, vp, pu64, vp]),
         "sf_fill_splitmix_device": (i32, [vp, u64, u64, u64, vp]),
         "sf_index_buffer": (i32, [vp, u64, u32, sig, u64, pu64]),
         "sf_index_buffer_blocks": (i32, [vp, u64, vp, vp, u64, sig, vp]),
         "sf_index_file_blocks": (i32, [cp, vp, vp, u64, sig, vp]),
         "sf_file_stamp_fd": (i32, [i32, stamp]),
+        "sf_read_fd_device": (i32, [i32, stamp, u64, u64, vp, pu64, vp]),
         "sf_index_fd_blocks": (i32, [i32, stamp, vp, vp, u64, sig, vp]),
         "sf_index_fd_fixed": (i32, [i32, stamp, u32, sig, u64, pu64, vp]),
         "sf_index_file": (i32, [cp, u32, sig, u64, pu64, vp]),
@@ -202,6 +205,7 @@ def _table():
         "sf_test_serve_files_stats": (i32, [vp]),
         "sf_test_block_data_stats": (i32, [vp]),
         "sf_test_copy_stats": (i32, [vp]),
+        "sf_test_plan_copies_stats": (i32, [vp]),
     }
     return public, test
 

@@ -11,11 +11,14 @@ temp file, filled by the block copy kernel (``device.copy_blocks``,
 sf_copy_blocks_device) in one launch per list, checked as a whole against the
 rows the source announced, and written to the temp file's descriptor
 (``device.write_to_fd``).  A job list that is on the device already -- the join
-of ``device.place_block_data`` -- goes in as it is (``apply_jobs``).
+of ``device.place_block_data``, the plan of ``device.plan_copies`` -- goes in as
+it is (``apply_jobs``).  ``LocalFiles`` is the source of the second: one HBM
+arena of the destination's own files, loaded with ``device.read_fd``.
 """
 from __future__ import annotations
 
 import hashlib
+import os
 from pathlib import Path
 from typing import Callable, Dict, List, Mapping, Optional
 
@@ -23,9 +26,10 @@ import numpy as np
 import torch
 
 from . import device as _device
+from ._lib import SF_EAGAIN, SF_EIO, FileStamp, SfError, lib
 from .index import _name_str
 
-__all__ = ["FileImages"]
+__all__ = ["FileImages", "LocalFiles"]
 
 
 def _rounds(jobs: List[tuple]) -> List[List[tuple]]:
@@ -55,6 +59,82 @@ def _rounds(jobs: List[tuple]) -> List[List[tuple]]:
             rounds.append([])
         rounds[r].append((s, at, size))
     return [r for r in rounds if r]
+
+
+class LocalFiles:
+    """One HBM arena of the local files a copy plan reads
+    (``device.plan_copies``), in the plan's numbering: file j is ``names[j]``.
+
+    ``stat(names)`` takes every file's size (a file that cannot be stat'ed gets
+    UNKNOWN_SIZE: no row in it is stale, and as it cannot be loaded either its
+    blocks are unavailable).  ``load(need)`` lays the files with
+    ``need[j] != 0`` (None: all) out at 256-byte-aligned bases of ONE
+    allocation, opens each, stamps its descriptor and reads it with
+    ``device.read_fd`` against that stamp.  A file that cannot be opened,
+    whose size is no longer the one ``stat`` saw, or that changed while it was
+    read gets the base UINT64_MAX (-1): the plan calls its blocks unavailable
+    and they are requested from the source.  ``bases()`` and ``sizes()`` are the
+    plan's ``local_base`` and ``local_size``, ``arena`` its ``src``."""
+
+    ALIGN = 256
+    NOT_LOADED = -1  # UINT64_MAX as the int64 the tensors hold
+    UNKNOWN_SIZE = (1 << 63) - 1
+
+    def __init__(self, root, device=None):
+        self.root = Path(root)
+        self.device = _device.device_of(device)
+        self.names: List[str] = []
+        self._sizes: List[int] = []
+        self._bases: List[int] = []
+        self.arena = torch.empty(0, dtype=torch.uint8, device=self.device)
+
+    def stat(self, names) -> "LocalFiles":
+        self.names = [_name_str(n) for n in names]
+        self._sizes = []
+        for name in self.names:
+            try:
+                self._sizes.append(os.stat(self.root / name).st_size)
+            except OSError:
+                self._sizes.append(self.UNKNOWN_SIZE)
+        self._bases = [self.NOT_LOADED] * len(self.names)
+        return self
+
+    def load(self, need=None, stream: Optional[torch.cuda.Stream] = None) -> int:
+        """Returns the number of files loaded.  One descriptor is open at a
+        time: the arena is laid out from the sizes ``stat`` took, and a file
+        whose descriptor shows another size is not read."""
+        wanted, at = {}, 0
+        for j in range(len(self.names)):
+            self._bases[j] = self.NOT_LOADED
+            if (need is None or need[j]) and self._sizes[j] != self.UNKNOWN_SIZE:
+                wanted[j] = at
+                at += (self._sizes[j] + self.ALIGN - 1) // self.ALIGN * self.ALIGN
+        with _device._on(self.device, stream):
+            self.arena = torch.empty(at, dtype=torch.uint8, device=self.device)
+        for j, base in wanted.items():
+            try:
+                fd = os.open(self.root / self.names[j], os.O_RDONLY)
+            except OSError:
+                continue
+            try:
+                stamp = FileStamp()
+                if lib().sf_file_stamp_fd(fd, stamp) != 0 or stamp.size != self._sizes[j]:
+                    continue
+                _device.read_fd(fd, stamp.size, 0, out=self.arena[base:base + stamp.size], stamp=stamp, stream=stream)
+            except SfError as e:
+                if e.code not in (SF_EAGAIN, SF_EIO):
+                    raise
+                continue
+            finally:
+                os.close(fd)
+            self._bases[j] = base
+        return len(self.names) - self._bases.count(self.NOT_LOADED)
+
+    def bases(self) -> torch.Tensor:
+        return torch.tensor(self._bases, dtype=torch.int64, device=self.device)
+
+    def sizes(self) -> torch.Tensor:
+        return torch.tensor(self._sizes, dtype=torch.int64, device=self.device)
 
 
 class FileImages:
@@ -162,6 +242,18 @@ class FileImages:
         (``buffer``): a row's ``dst`` for ``device.place_block_data`` is this
         plus the row's offset."""
         return self._place(name, 0, 0)
+
+    def bases(self, names) -> torch.Tensor:
+        """``base(name)`` of every name, in order, as an int64 tensor on the
+        images' device: ``device.plan_copies``' ``file_base``."""
+        return torch.tensor([self.base(n) for n in names], dtype=torch.int64, device=self.device)
+
+    def note_present(self, name, offsets) -> None:
+        """The offsets of ``name``'s rows that were recorded as present when
+        its FILE_END came, by a caller that filled them through ``apply_jobs``
+        (``apply_copies`` notes its own): ``check`` chains the digests in the
+        order that fixes."""
+        self._copied.setdefault(_name_str(name), set()).update(int(o) for o in offsets)
 
     def apply_jobs(self, src: torch.Tensor, src_offsets: torch.Tensor, dst_offsets: torch.Tensor,
                    sizes: torch.Tensor, stream: Optional[torch.cuda.Stream] = None) -> None:

@@ -1,7 +1,8 @@
 // sf_host_out.cpp -- the C-ABI's device-to-descriptor writers
 // (include/syncfast_amd.h): FILE_BLOCK runs built on the device, device bytes
 // and built BLOCK_DATA runs, each brought back through two pinned buffers and
-// written to the caller's descriptor while the next buffer is on the link.
+// written to the caller's descriptor while the next buffer is on the link;
+// and the way back, a descriptor's bytes read into HBM through the same buffers.
 // HIP runtime API only: built with the host compiler.
 #include <errno.h>
 #include <unistd.h>
@@ -226,6 +227,51 @@ int sf_write_device_fd(const void* d_data, uint64_t len, int fd, uint64_t file_o
           if (r == SF_OK) w.written += m;
           return r;
         });
+  });
+}
+
+// The other direction, the loader of the destination's local files: bytes
+// [file_offset, + len) of fd to d_dst[0, len).  Stage k is read with pread, in
+// slices on the pool threads, into pinned buffer k & 1 and copied from there
+// on the caller's own stream, while stage k-1's copy is on the link; buffer
+// k & 1 is read into again once the copy of stage k-2 is known done.  The
+// whole read lies between two stamps of the file (stamped).  *n_read counts
+// whole stages known copied.
+int sf_read_fd_device(int fd, const sf_file_stamp* expect, uint64_t file_offset, uint64_t len, void* d_dst,
+                      uint64_t* n_read, void* stream) {
+  return guarded([&] {
+    if (n_read) *n_read = 0;
+    if (fd < 0) return SF_EINVAL;
+    if (lseek(fd, 0, SEEK_CUR) == (off_t)-1 && errno == ESPIPE) return SF_EINVAL;  // pread would refuse it too
+    if (len && !d_dst) return SF_EINVAL;
+    return stamped(fd, expect, [&](const sf_file_stamp&, mode_t) {
+      if (len == 0) return SF_OK;
+      const uint64_t stage = out_stage_bytes(len);
+      hipStream_t cs = as_stream(stream);
+      WireOut w(fd);
+      int rc = w.open(stage, false);
+      if (rc != SF_OK) return rc;
+      rc = two_stage(
+          ceil_div(len, stage),
+          [&](uint64_t k, int b) {
+            const uint64_t m = std::min(stage, len - k * stage);
+            w.bytes_of[b] = m;
+            const int r = read_sliced(fd, static_cast<uint8_t*>(w.sb[b].pin), file_offset + k * stage, m);
+            if (r != SF_OK) return r;
+            SF_HIP(hipMemcpyAsync(static_cast<uint8_t*>(d_dst) + k * stage, w.sb[b].pin, m, hipMemcpyHostToDevice,
+                                  cs));
+            SF_HIP(hipEventRecord(w.ev[b], cs));
+            return SF_OK;
+          },
+          [&](uint64_t, int b) {
+            SF_HIP(hipEventSynchronize(w.ev[b]));
+            w.written += w.bytes_of[b];
+            return SF_OK;
+          });
+      (void)hipStreamSynchronize(cs);  // whatever came of it: no copy still reads a pinned buffer
+      if (n_read) *n_read = w.written;
+      return rc;
+    });
   });
 }
 

@@ -20,7 +20,8 @@
 //                 streams and staging buffers, the buffer / file / fd / range
 //                 pipelines, stamp and host SHA-1 helpers;
 //   sf_host_out.cpp  the device-to-descriptor writers: FILE_BLOCK runs,
-//                 device bytes and BLOCK_DATA runs streamed to an fd;
+//                 device bytes and BLOCK_DATA runs streamed to an fd; and the
+//                 descriptor-to-device loader of the local files;
 //   sf_pagelock.cpp  the registry of host ranges page-locked by the in-place
 //                 routes (the region rule itself is sf_inplace.hpp: host
 //                 arithmetic, executed by tests/native/inplace_regions.cpp);
@@ -69,6 +70,11 @@
 //                 own kernels; the rules are sf_wire_get_files.hpp; the newline
 //                 bitmap is sf_recv_scan.hpp's, the lookup sf_names.hip's, the
 //                 block scan sf_wire.hip's).
+//   sf_plan_copies.hip  the received blocks the destination already holds
+//                 turned into a copy list and the rows' present flags in one
+//                 call, each local block hashed before it is used (its own
+//                 kernels; the rules are sf_plan_copies.hpp; the hashing is
+//                 sf_table.hip's).
 // Every .hip file launches its kernels and runs its rocprim scans through
 // sf_device.hpp (launch, grid256, scan_inclusive, scan_exclusive), and divides
 // its scratch with sf_layout.hpp (ScratchLayout, for_pieces: host arithmetic,

@@ -37,7 +37,7 @@ __all__ = [
     "cut_zpaq_files", "index_zpaq_files", "zpaq_files_stats", "ZpaqFiles",
     "copy_blocks", "copy_stats", "write_to_fd", "get_block_requests", "place_block_data",
     "device_of", "upload", "NameSet", "EntriesReceived", "receive_file_entries", "pack_names", "file_entries_stats",
-    "FilesServed", "serve_files_stats",
+    "FilesServed", "serve_files_stats", "read_fd", "plan_copies", "plan_copies_stats", "CopyPlan", "PlanCounts",
 ]
 
 
@@ -1218,6 +1218,138 @@ def write_to_fd(t: torch.Tensor, fd: int, offset: int = 0, stream: Optional[torc
         err.written = nw.value
         raise err
     return nw.value
+
+
+def read_fd(fd: int, length: int, offset: int = 0, out: Optional[torch.Tensor] = None, stamp=None,
+            device=None, stream: Optional[torch.cuda.Stream] = None) -> torch.Tensor:
+    """Bytes [offset, offset + length) of the open file ``fd`` as a uint8 HBM
+    tensor (sf_read_fd_device, the twin of ``write_to_fd``: pread by the
+    library's threads into pinned stages, copied on ``stream`` while the next
+    stage is read; the descriptor's position is not used or moved).  ``out``: a
+    uint8 HBM tensor of at least ``length`` bytes to read into (any address);
+    its first ``length`` bytes are returned.  ``stamp``: the ``FileStamp`` the
+    caller took of the file; a file that is another, or that changes during
+    the read, raises SfError(SF_EAGAIN), one shorter than asked SfError(SF_EIO),
+    a descriptor that cannot seek SfError(SF_EINVAL).  Blocking."""
+    length = int(length)
+    if length < 0 or offset < 0:
+        raise ValueError("length and offset must not be negative")
+    if out is not None:
+        _require_device(out, "out", torch.uint8)
+        if out.numel() < length:
+            raise ValueError(f"out holds {out.numel()} bytes, need {length}")
+    dev = out.device if out is not None else device_of(device)
+    with _on(dev, stream):
+        t = out if out is not None else torch.empty(length, dtype=torch.uint8, device=dev)
+        check(lib().sf_read_fd_device(int(fd), ctypes.byref(stamp) if stamp is not None else None, int(offset), length,
+                                      _ptr(t, length), None, _stream_ptr(t, stream)), "sf_read_fd_device")
+    return t[:length]
+
+
+class PlanCounts(NamedTuple):
+    """counts of sf_plan_copies_device, in the order of its SF_PLAN_* indices."""
+    jobs: int
+    bytes: int
+    missing: int
+    size_mismatch: int
+    stale: int
+    unavailable: int
+    unverified: int
+    empty: int
+
+
+class CopyPlan(NamedTuple):
+    """What ``plan_copies`` returns.  Per block: ``present`` uint8[n], ``ask``
+    uint8[n] (``get_block_requests``' ``take``), ``dst`` int64[n]
+    (``place_block_data``'s ``row_dst``).  The jobs in block order, one
+    ``copy_blocks`` call: ``src_offsets`` / ``dst_offsets`` int64[k], ``sizes``
+    int32[k], ``job_blocks`` int64[k].  ``local_jobs`` int32[n_local]: the jobs
+    that read each local file.  A query has None for everything but
+    ``local_jobs`` and ``counts``."""
+    present: Optional[torch.Tensor]
+    ask: Optional[torch.Tensor]
+    dst: Optional[torch.Tensor]
+    src_offsets: Optional[torch.Tensor]
+    dst_offsets: Optional[torch.Tensor]
+    sizes: Optional[torch.Tensor]
+    job_blocks: Optional[torch.Tensor]
+    local_jobs: torch.Tensor
+    counts: PlanCounts
+
+
+def plan_copies_stats() -> Tuple[int, int, int, int]:
+    """(read-backs, candidates hashed, jobs, 1 for a query) of this process's
+    last ``plan_copies`` (sf_test_plan_copies_stats)."""
+    out = (ctypes.c_uint64 * 4)()
+    check(lib().sf_test_plan_copies_stats(out), "sf_test_plan_copies_stats")
+    return tuple(int(v) for v in out)
+
+
+def plan_copies(digests: torch.Tensor, sizes: torch.Tensor, offsets: torch.Tensor, rows: torch.Tensor,
+                block_file: torch.Tensor, file_base: torch.Tensor, table_file: torch.Tensor,
+                table_offset: torch.Tensor, table_size: torch.Tensor, local_size: torch.Tensor,
+                local_base: Optional[torch.Tensor] = None, src: Optional[torch.Tensor] = None,
+                stream: Optional[torch.cuda.Stream] = None) -> CopyPlan:
+    """The blocks of a received GetFiles stream that the destination already
+    holds, turned into one copy list on the device (sf_plan_copies_device):
+    the sink's per-block get_block / read_block / write_block / add_block
+    (src/sync/fs.rs:461-471) as one call, with every local block hashed and
+    compared with the digest the source announced before it is used.
+
+    Blocks: the first five results of ``BlockSet.receive_files``;
+    ``file_base`` int64[m] where each section's byte 0 lies in the image
+    allocation (``FileImages.bases``).  The table the set was built from, in
+    rowid order: ``table_file`` int32[t] the local file holding each row (the
+    caller's numbering), ``table_offset`` int64[t], ``table_size`` int32[t].
+    Local files: ``local_size`` int64[l] and ``local_base`` int64[l], where
+    each lies in the arena ``src`` (-1, i.e. UINT64_MAX: not loaded).
+
+    ``local_base`` None is a query: only ``local_jobs`` -- how many jobs would
+    read each local file, the files worth loading -- and ``counts`` come back.
+    ``src`` None plans without verification.  A block found in a row of another
+    size, in a file shorter than the row says, in a file that is not loaded, or
+    whose bytes no longer hash to its digest keeps present = 0 and asks the
+    source.  Blocking: one read-back, two with verification."""
+    n = _table20(digests, "digests")
+    dev = digests.device
+    _list32(sizes, "sizes", n, dev)
+    _list64(offsets, "offsets", n, dev)
+    _list64(rows, "rows", n, dev)
+    _list32(block_file, "block_file", n, dev)
+    m, t, nl = file_base.numel(), table_file.numel(), local_size.numel()
+    _list64(file_base, "file_base", m, dev)
+    _list32(table_file, "table_file", t, dev)
+    _list64(table_offset, "table_offset", t, dev)
+    _list32(table_size, "table_size", t, dev)
+    _list64(local_size, "local_size", nl, dev)
+    query = local_base is None
+    if not query:
+        _list64(local_base, "local_base", nl, dev)
+    if src is not None:
+        _require_device(src, "src", torch.uint8, dev)
+    counts = (ctypes.c_uint64 * 8)()
+    with _on(dev, stream):
+        local_jobs = torch.empty(nl, dtype=torch.int32, device=dev)
+        e = lambda k, dt: None if query else torch.empty(k, dtype=dt, device=dev)  # noqa: E731
+        present, ask, dst = e(n, torch.uint8), e(n, torch.uint8), e(n, torch.int64)
+        so, do, jb, js = e(n, torch.int64), e(n, torch.int64), e(n, torch.int64), e(n, torch.int32)
+        # no local file at all is not a query: the library tells the two apart by the pointer
+        lb = local_base if query or nl else torch.zeros(1, dtype=torch.int64, device=dev)
+        rc = lib().sf_plan_copies_device(
+            _ptr(digests, n), _ptr(sizes, n), _ptr(offsets, n), _ptr(rows, n), _ptr(block_file, n), n,
+            _ptr(file_base), m, _ptr(table_file), _ptr(table_offset), _ptr(table_size), t,
+            None if query else lb.data_ptr(), _ptr(local_size), nl,
+            _ptr(src) if src is not None and not query else None, src.numel() if src is not None else 0,
+            _ptr(present), _ptr(ask), _ptr(dst), _ptr(so), _ptr(do), _ptr(js), _ptr(jb), 0 if query else n,
+            _ptr(local_jobs), counts, _stream_ptr(digests, stream))
+    c = PlanCounts(*(int(v) for v in counts))
+    if query:
+        if rc not in (0, SF_ENOSPC):
+            check(rc, "sf_plan_copies_device")
+        return CopyPlan(None, None, None, None, None, None, None, local_jobs, c)
+    check(rc, "sf_plan_copies_device")
+    k = c.jobs
+    return CopyPlan(present, ask, dst, so[:k], do[:k], js[:k], jb[:k], local_jobs, c)
 
 
 def fill_splitmix(out: torch.Tensor, seed: int, start: int = 0,

@@ -582,6 +582,84 @@ class Index:
             copies.setdefault(name, []).extend(found_here)
         return copies, r.consumed, ((ids[-1], r.end_offset) if r.open else None)
 
+    def receive_files_assembled(self, data, root, device=None, verify: bool = True):
+        """``receive_files`` and the copies it lists in one, with the step
+        between them on the device: a WHOLE GetFiles stream -- it begins with a
+        FILE_START and ends with a FILE_END, no file carried in or out;
+        anything else raises ValueError -- is parsed and looked up as
+        ``receive_files`` does, the blocks found become one copy plan
+        (``device.plan_copies``: first a query for the local files worth
+        loading, then ``assemble.LocalFiles`` loads those below ``root`` with
+        ``device.read_fd``, then the plan itself), ``assemble.FileImages`` is
+        built from the sections' sizes and filled by ONE ``apply_jobs``, and ONE
+        executemany inserts every block with the plan's present flag.
+
+        With ``verify`` every local block is hashed on the device and compared
+        with the digest the source announced before it is copied; one that
+        differs -- the file was edited after it was indexed -- keeps
+        present = 0, so ``get_block_requests`` asks the source for it.  The
+        same goes for a block found in a row of another size, in a file now
+        shorter than the row says, and in a file that cannot be read (the
+        image of a temp file of this same sync among them).  On honest input
+        the database ends as ``receive_files`` leaves it.
+
+        Returns (images, plan, consumed): the ``FileImages``, the
+        ``device.CopyPlan`` (per-block ``present`` / ``ask`` / ``dst`` and the
+        counts) and the bytes of the stream.  Raises what ``receive_files``
+        raises; in every raising case nothing is written."""
+        from . import wire
+        from .assemble import FileImages, LocalFiles
+        from . import device as _device
+        data = bytes(data)
+        if data and not (data.startswith(b"FILE_START\n") and data.endswith(b"FILE_END\n")):
+            raise ValueError("receive_files_assembled takes a whole GetFiles stream: no file carried in or out")
+        import torch
+        with self._block_set(device) as (rows, bset):
+            dev = bset.table.device
+            r = bset.receive_files(_device.upload(data, dev))
+            _stop_error(r.stop, r.consumed, "GetFiles stream", r.stop in (wire.SF_WIRE_UNEXPECTED, wire.SF_WIRE_OTHER),
+                        "Unexpected message from source")
+            if r.open or r.consumed != len(data):
+                raise ValueError("receive_files_assembled takes a whole GetFiles stream: it ends inside a file")
+            ids = []
+            for at, n in zip(r.name_at.cpu().tolist(), r.name_len.cpu().tolist()):
+                try:
+                    name = data[at:at + n].decode("utf-8")
+                except UnicodeDecodeError:
+                    raise wire.ProtocolError("Bad filename encoding (byte %d)" % at) from None
+                temp = self.get_temp_file(PurePath(name))
+                if temp is None:
+                    raise SyncfastError("Unknown file %r" % name)
+                ids.append(temp[0])
+            names = [self.get_file_name(i) for i in ids]
+            if len(set(names)) != len(names):
+                raise ValueError("a file is sent twice in one stream: use receive_files")
+            file_size = r.file_size.cpu().tolist()
+            # the table's rows by the local file that holds each (rows of no file are never found)
+            number: dict = {}
+            table_file = np.fromiter((number.setdefault(q[2], len(number)) if q[2] is not None else 0 for q in rows),
+                                     np.int32, len(rows))
+            up = lambda a: torch.from_numpy(a).to(dev)  # noqa: E731
+            table = (up(table_file), up(np.fromiter((q[3] for q in rows), np.int64, len(rows))),
+                     up(np.fromiter((q[4] for q in rows), np.uint32, len(rows)).view(np.int32)))
+            local = LocalFiles(root, dev).stat(list(number))
+            images = FileImages(dict(zip(names, file_size)), dev, root)
+            blocks = (r.digests, r.sizes, r.offsets, r.rows, r.block_file, images.bases(names))
+            query = _device.plan_copies(*blocks, *table, local.sizes())
+            local.load(query.local_jobs.cpu().numpy())
+            plan = _device.plan_copies(*blocks, *table, local.sizes(), local.bases(),
+                                       local.arena if verify else None)
+            images.apply_jobs(local.arena, plan.src_offsets, plan.dst_offsets, plan.sizes)
+            digests, sizes, offsets, block_file, present = (
+                t.cpu().numpy() for t in (r.digests, r.sizes, r.offsets, r.block_file, plan.present))
+        self.begin()
+        self.db.executemany(INSERT_BLOCK, ((bytes(d).hex(), ids[f], int(o), int(s), int(p))
+                                           for d, f, o, s, p in zip(digests, block_file, offsets, sizes, present)))
+        for f, file_id in enumerate(ids):
+            self.set_file_size_and_compute_blocks_hash(file_id, int(file_size[f]))
+            images.note_present(names[f], offsets[(block_file == f) & (present != 0)])
+        return images, plan, r.consumed
+
     def apply_block_data(self, digests, sizes, data_offsets, ok=None):
         """The database half of ``receive_block_data``, from the parsed arrays
         (no GPU): for each message in order whose payload verified (``ok``
